@@ -11,10 +11,18 @@ The frames are resident in HBM before the timed region starts.  With N ranks eve
 own sequence (independent sequences are the unit the path shards on: SURVEY.md §8e) -- weak scaling,
 no data-path collective; only the barrier / max-time reduction use RCCL.
 
-Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel (by accumulated GPU time,
-measured with HIP events on the kernel's own stream inside the library); `cpu_baseline` is the real
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`, the counters of the last timed pass).  Everything that takes runs of its own
+comes only with --full: `roofline` describes the dominant kernel (by accumulated GPU time, measured
+with HIP events on the kernel's own stream inside the library, in one extra pass); `batched`,
+`sharded_ba` / `sharded_sequence` and the ATE of the keyframe centres; `cpu_baseline` is the real
 reference binary (oracle/_ref, kind "reference") or, when that is absent, the oracle restatement
 (kind "port") timed on a bounded sample of the same workload on this host's cores.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float64):
+`centres` (keyframe camera centres) and `counts` (keyframes, map points, pose-graph edges, frames) of
+rank 0's sequence, `centres_seq<q>` / `counts_seq<q>` for further sequences in flight; `dx` in
+--mode ba-sharded.  The inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -78,7 +86,13 @@ def cpu_baseline(seq, cfg, sample_frames: int):
                 frames_per_s=sample_frames / dt)
 
 
-def run_ba_sharded(capi, synth, rank, local_rank, world, steps, warmup, ctx=None, comm=None, shard="elements"):
+def dump_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def run_ba_sharded(capi, synth, rank, local_rank, world, steps, warmup, ctx=None, comm=None, shard="elements", dump_dir=None):
     """BASELINE config C4: local BA on W=10 poses, P=50 000 points, every point seen by every pose (500 k residuals), sharded
     over the ranks; a step = one BA iteration = build of this rank's share of S|b, RCCL all-reduce(sum) of D*D + D = 3 660
     doubles in HBM, damping + gauge, dense solve on the device, dx to the host.
@@ -133,6 +147,8 @@ def run_ba_sharded(capi, synth, rank, local_rank, world, steps, warmup, ctx=None
         t = torch.tensor([dt], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"dx": dx})
     ctx.set_timing(True)
     for _ in range(3):
         step(comm, *a)
@@ -175,7 +191,8 @@ def bench_ba_sharded(args, capi, synth, rank, local_rank, world):
     import torch.distributed as dist
     if world > 1:
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    out = run_ba_sharded(capi, synth, rank, local_rank, world, args.steps, args.warmup, shard=args.ba_shard)
+    out = run_ba_sharded(capi, synth, rank, local_rank, world, args.steps, args.warmup, shard=args.ba_shard,
+                         dump_dir=args.dump_outputs)
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
@@ -191,16 +208,21 @@ def main():
     ap.add_argument("--frames", type=int, default=47)
     ap.add_argument("--deg-per-frame", type=float, default=0.3)
     ap.add_argument("--max-tracks", type=int, default=2200)
-    ap.add_argument("--cpu-sample-frames", type=int, default=12)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also take the roofline pass, the batched and sharded probes, the ATE of the "
+                         "keyframe centres and the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-sample-frames", type=int, default=12, help="--full: frames of the CPU baseline's sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--sequences-per-gpu", type=int, default=1,
                     help="independent sequences in flight on each GPU (a batch of S sequences per step); the headline uses 1")
     ap.add_argument("--batched-probe", type=int, default=3,
-                    help="after the headline measurement (1 sequence per GPU) also time this many sequences in flight and "
-                         "report it as `batched` (single-GPU runs only; 0 = skip)")
+                    help="--full: after the headline measurement (1 sequence per GPU) also time this many sequences in flight "
+                         "and report it as `batched` (single-GPU runs only; 0 = skip)")
     ap.add_argument("--sharded-probe", type=int, default=1,
-                    help="default mode: after the headline also time the sharded BA step (C4) and one sequence on all ranks and "
-                         "report them as `sharded_ba` / `sharded_sequence` (0 = skip)")
+                    help="--full, default mode: after the headline also time the sharded BA step (C4) and one sequence on all "
+                         "ranks and report them as `sharded_ba` / `sharded_sequence` (0 = skip)")
     ap.add_argument("--ba-shard", choices=("elements", "points"), default="elements",
                     help="--mode ba-sharded: elements (parity mode, sfmx_ba_step_sharded_elements) or points (tolerance mode)")
     ap.add_argument("--sharded-timeout", type=float, default=240.0, help="watchdog of the sharded sub-benchmarks, seconds")
@@ -210,6 +232,8 @@ def main():
                          "RCCL all-reduce of S|b per iteration (strong scaling); sharded-sequence: ONE sequence on all ranks, BA points "
                          "and RANSAC hypotheses sharded (strong scaling)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -312,9 +336,10 @@ def main():
             c.sync()
         barrier()
         wall = time.perf_counter() - t_start
-        return wall, sum(r["kf"] for r in result), all(r["identical"] for r in result), result[0]["last"]
+        return wall, sum(r["kf"] for r in result), all(r["identical"] for r in result), [r["last"] for r in result]
 
-    dt, kf_total, identical, last = measure(S, args.warmup, args.steps)
+    dt, kf_total, identical, lasts = measure(S, args.warmup, args.steps)
+    last = lasts[0]
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -325,7 +350,8 @@ def main():
             kf_total = int(k.item())
 
     # --- one extra, untimed pass with per-kernel HIP-event timing for the roofline object
-    prof = one_pass(timing=True)["stats"]
+    if args.full:
+        prof = one_pass(timing=True)["stats"]
 
     # --- the north_star's split, measured by the SAME command with the same process group (default mode only): BA points
     # sharded with an RCCL all-reduce of S | b per iteration (BASELINE config C4), and ONE sequence on all ranks with BA points
@@ -334,7 +360,7 @@ def main():
     # not cost the headline line (the sub-object then says so and the process leaves without the RCCL teardown).
     sharded = {"sharded_ba": None, "sharded_sequence": None}
     sub_failed = []
-    if args.mode == "sequences" and args.sharded_probe:
+    if args.full and args.mode == "sequences" and args.sharded_probe:
         def sub_benchmarks():
             Dm = importlib.import_module(PKG + ".dist")
             # C4 through sfmx_ba_step_sharded
@@ -405,13 +431,13 @@ def main():
                     sharded[k] = {"error": f"no result within {args.sharded_timeout} s (watchdog)", "rccl_world": world}
                     sub_failed.append(k)
     batched = None
-    if world == 1 and S == 1 and args.batched_probe > 1:  # how much more the device takes with several sequences in flight
+    if args.full and world == 1 and S == 1 and args.batched_probe > 1:  # how much more the device takes with several sequences in flight
         b_steps = max(2, min(args.steps, 8))
         b_dt, b_kf, b_same, _ = measure(args.batched_probe, 1, b_steps)
         batched = {"sequences_per_gpu": args.batched_probe, "value": round(b_kf / b_dt, 3), "unit": "keyframes/s", "steps": b_steps,
                    "ms_per_step": round(b_dt / b_steps * 1e3, 3), "passes_bit_identical": bool(b_same)}
-    if rank == 0:
-        st = last["stats"]
+    st = last["stats"]
+    if rank == 0 and args.full:
         # --- roofline of the DOMINANT kernel of this run: the kernel with the largest accumulated GPU time in the
         # per-kernel profile of the extra timed pass (HIP events recorded inside libsfmx on each context's own stream
         # around every launch, summed over the contexts of the pipeline).  Nothing here is read from a previous
@@ -500,6 +526,7 @@ def main():
                                          frac=round(tf / FP64_VALU_PEAK_TF, 5))
             except Exception as e:  # the line must still be printed
                 roofline["alone"] = {"error": repr(e)}
+    if rank == 0:
         out = {
             "metric": "keyframes/sec (KLT + RANSAC + local BA per-frame loop), synthetic TempleRing-47 stand-in",
             "value": round(kf_total / dt, 3), "unit": "keyframes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -515,8 +542,9 @@ def main():
             "keyframes_per_step": int(round(kf_total / max(1, args.steps) / (1 if args.mode == "sharded-sequence" else world))), "map_points": st["n_points"], "passes_bit_identical": bool(identical),
             "host_seconds_per_step": {k: round(st[k], 4) for k in ("sec_wall", "sec_total", "sec_setup", "sec_klt", "sec_shi", "sec_shi_wait", "sec_shi_gpu", "sec_shi_replay", "sec_ransac", "sec_ba", "sec_upload", "sec_host", "sec_desc", "sec_bookkeeping", "sec_r_pre", "sec_r_gpu", "sec_r_verify", "sec_r_decomp", "sec_tri_iter", "sec_tri_solve", "sec_tri_insert", "sec_pf_busy", "sec_pf_gpu", "sec_pf_replay", "sec_lane_a_busy", "sec_lane_b_busy", "sec_lane_c_busy", "sec_lane_e_busy", "sec_join_wait", "sec_ba_gather", "sec_m_step", "sec_m_ransac", "sec_m_kf", "sec_feed_wait")},
             "counters_per_step": {k: int(st[k]) for k in ("klt_calls", "tracks_in", "lk_steps", "ransac_calls", "ransac_points", "ransac_verified", "ransac_cert_misses", "ba_calls", "ba_iters", "shi_calls", "shi_memo_hits", "shi_prefetched", "shi_fallbacks")},
-            "roofline": roofline,
         }
+    if rank == 0 and args.full:
+        out["roofline"] = roofline
         # ATE-RMSE of the keyframe centres against the synthetic ground truth, stated by the build's own evaluator
         # (structure-from-motion-3d-reconstruction_amd/_build/ate_keyframes; its digits are pinned to the reference tool's
         # in tests/test_tools.py) on the CSV of one extra, untimed pass
@@ -544,6 +572,15 @@ def main():
             cb = cpu_baseline(seq, cfg, min(args.cpu_sample_frames, args.frames))
             out["cpu_baseline"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in cb.items()}
             out["speedup_vs_cpu_baseline"] = round(out["value"] / cb["value"], 1) if cb["value"] > 0 else None
+    if rank == 0:
+        if args.dump_outputs:
+            arrays = {}
+            for q, r in enumerate(lasts):
+                sfx = "" if q == 0 else f"_seq{q}"
+                s_ = r["stats"]
+                arrays["centres" + sfx] = r["centres"]
+                arrays["counts" + sfx] = [s_["n_keyframes"], s_["n_points"], s_["n_edges"], s_["n_frames"]]
+            dump_outputs(args.dump_outputs, arrays)
         print(json.dumps(out))
     sys.stdout.flush()
     if sub_failed:  # a collective is stuck somewhere: no barrier, no RCCL teardown -- the line is out, leave

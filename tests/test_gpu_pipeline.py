@@ -79,6 +79,31 @@ def test_bench_workload_47_frames_vs_oracle(ctx, tmp_path):
     assert r["stats"]["n_keyframes"] == nk and r["stats"]["n_points"] == npnt
 
 
+def test_bench_plain_line_and_dumped_outputs(ctx, tmp_path):
+    """A plain bench.py run prints the headline keys and none of the --full objects; --dump-outputs holds what the last
+    timed pass returned, bit for bit what one pipeline run on the same seeded sequence returns."""
+    import sys
+    d = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--frames", "12", "--dump-outputs", str(d)], capture_output=True, text=True, cwd=H.ROOT, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 2 and line["passes_bit_identical"] and line["ms_per_step"] > 0
+    assert not {"roofline", "batched", "sharded_ba", "sharded_sequence", "cpu_baseline"} & set(line)
+    seq = synth.make_sequence(12, 640, 480, 0.3, n_blobs=20000, seed=7)
+    cfg = dict(pipe.DEFAULTS, frames=12, max_tracks=2200, min_tracks=900, export_pointcloud=0)
+    r = pipe.run(ctx, seq["images"], seq["names"], seq["K"], seq["lat"], seq["lon"], cfg, None)
+    c = np.load(d / "centres.npy")
+    assert c.dtype == np.float64 and len(c) >= 2
+    H.assert_bits_equal(c, r["centres"], "bench --dump-outputs centres")
+    st = r["stats"]
+    counts = np.load(d / "counts.npy")
+    assert counts.dtype == np.float64
+    assert np.array_equal(counts, [st["n_keyframes"], st["n_points"], st["n_edges"], st["n_frames"]])
+
+
 def test_two_keyframe_pair_ate_two_frames(ctx, tmp_path):
     """BASELINE config 1: a 2-keyframe 640x480 pair (KLT + RANSAC + triangulate) checked with ate_two_frames
     (cpp/tools/ate_two_frames.cpp; the build's tool is pinned to the reference tool digit for digit in

@@ -5,7 +5,7 @@ VAR=$1; VALS=$2; REPS=${3:-3}
 for rep in $(seq $REPS); do
   for v in $VALS; do
     if [ "$v" = "-" ]; then unset $VAR; else export $VAR=$v; fi
-    echo "$VAR=$v: $(python bench.py --no-cpu-baseline --batched-probe 0 --steps 10 2>/dev/null | python -c "
+    echo "$VAR=$v: $(python bench.py --full --no-cpu-baseline --batched-probe 0 --steps 10 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); h=d['host_seconds_per_step']; r=d['roofline']
 shi=r['kernel_us_per_pass'].get('shi fixpoint (k_shi_round / k_shi_list_* / k_shi_tail)',0)

@@ -9,7 +9,7 @@ cd "$(dirname "$0")/.."
 OUT=gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT" profiles
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --batched-probe 0 > "$OUT/bench_trace.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_trace" -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --batched-probe 0 > "$OUT/bench_trace.log" 2>&1
 echo "bench trace done"
 export SFMX_PROF_META="$PWD/profiles/${TAG}_pmc_meta.json"
 export SFMX_PROF_C4=1
@@ -21,7 +21,7 @@ rocprofv3 --pmc SQ_INSTS_MFMA SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCL
 echo "pmc passes done"
 python tools/summarize_profiles.py "$TAG" "$OUT/bench_trace" "$OUT/pmc"
 # the bench line last: its roofline object quotes the PMC summary written just above (same code, same box)
-python bench.py > "$OUT/bench_line.json" 2> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 cp "$OUT/bench_line.json" "profiles/${TAG}_bench_line.json"
 echo "bench line done"
 python tools/microbench.py > "profiles/${TAG}_microbench.txt" 2>&1

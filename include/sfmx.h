@@ -245,6 +245,35 @@ uint64_t sfmx_debug_klt_slow_steps(const sfmx_ctx* ctx);
 int sfmx_posegraph_solve(sfmx_ctx* ctx, int n, const int32_t* entry_ij, const double* entry_v, int m,
                          const double* g3, double* x3);
 
+/* ---- keyframe-pair stereo: rectification + census SGM (not in the reference's C++) ------------------------ */
+/* Every stage is integer arithmetic or IEEE double with a fixed expression order, so the disparity map is bit-identical to
+ * the NumPy restatement in tests/stereo_ref.py.  Stages: bilinear remap through H (rectified pixel -> source pixel), census
+ * transform, Hamming cost, 4-path SGM (left->right, right->left, top->bottom, bottom->top) summed into S (u16), winner with
+ * uniqueness test, integer sub-pixel refinement, left-right check, speckle filter (4-connected components). */
+typedef struct sfmx_stereo sfmx_stereo;  /* device buffers for one (w, h, params) */
+typedef struct sfmx_stereo_params {
+  int num_disparities; /* D: multiple of 16, 16..256 */
+  int census;          /* census window side: 3, 5 or 7 */
+  int p1, p2;          /* SGM penalties, 0 < p1 < p2 <= 2048 (defaults 8, 96) */
+  int uniqueness;      /* percent, 0..100 (default 10; 0 = off) */
+  int lr_max_diff;     /* left-right check in whole pixels (default 1; < 0 = off) */
+  int speckle_window;  /* components with fewer pixels become invalid (default 100; 0 = off) */
+  int speckle_range;   /* max disparity step inside a component, whole pixels (default 2) */
+} sfmx_stereo_params;
+void sfmx_stereo_default_params(sfmx_stereo_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_stereo_check_params(int w, int h, const sfmx_stereo_params* p);
+int sfmx_stereo_create(sfmx_ctx* ctx, int w, int h, const sfmx_stereo_params* p, sfmx_stereo** out);
+void sfmx_stereo_destroy(sfmx_ctx* ctx, sfmx_stereo* st);
+/* img_l / img_r: u8 [h][w], host pointers or (on_device = 1) device pointers.
+ * H_l, H_r: row-major 3x3 maps from a rectified pixel to a source pixel.
+ * disp16_out: int16 [h][w] on the host, disparity x 16 in the left rectified view, -16 = invalid.
+ * rect_out (optional): u8 [2][h][w] rectified images.  sum_out (optional): u16 [h][w][D] aggregated cost S. */
+int sfmx_stereo_disparity(sfmx_ctx* ctx, sfmx_stereo* st, const uint8_t* img_l, const uint8_t* img_r, int on_device,
+                          const double* H_l, const double* H_r, int16_t* disp16_out, uint8_t* rect_out, uint16_t* sum_out);
+/* device time (us) of the kernels of the last sfmx_stereo_disparity call when timing is on (sfmx_set_timing), else 0 */
+double sfmx_stereo_last_us(const sfmx_stereo* st);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

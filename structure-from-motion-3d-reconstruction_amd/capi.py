@@ -30,6 +30,8 @@ SYMBOLS = [
     "sfmx_comm_get_unique_id", "sfmx_comm_create", "sfmx_comm_destroy", "sfmx_comm_rank", "sfmx_comm_world", "sfmx_shard_range",
     "sfmx_comm_allreduce_f64", "sfmx_comm_allreduce_u64_max",
     "sfmx_debug_hypot", "sfmx_debug_divsqrt", "sfmx_debug_klt_slow_steps",
+    "sfmx_stereo_default_params", "sfmx_stereo_check_params", "sfmx_stereo_create", "sfmx_stereo_destroy", "sfmx_stereo_disparity",
+    "sfmx_stereo_last_us",
 ]
 
 
@@ -41,6 +43,26 @@ class SfmxError(RuntimeError):
 
 class KltCfg(ctypes.Structure):
     _fields_ = [("levels", c_int), ("win_radius", c_int), ("iters", c_int), ("fb_thresh", c_double)]
+
+
+class StereoParams(ctypes.Structure):
+    _fields_ = [("num_disparities", c_int), ("census", c_int), ("p1", c_int), ("p2", c_int), ("uniqueness", c_int),
+                ("lr_max_diff", c_int), ("speckle_window", c_int), ("speckle_range", c_int)]
+
+
+STEREO_DEFAULTS = dict(num_disparities=128, census=5, p1=8, p2=96, uniqueness=10, lr_max_diff=1, speckle_window=100, speckle_range=2)
+
+
+def stereo_params(**kw) -> StereoParams:
+    unknown = set(kw) - set(STEREO_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown stereo parameters {sorted(unknown)}")
+    return StereoParams(**{**STEREO_DEFAULTS, **kw})
+
+
+def stereo_check_params(w: int, h: int, **kw) -> bool:
+    """True if sfmx_stereo_create would accept (w, h, params); needs no device"""
+    return load_library().sfmx_stereo_check_params(c_int(w), c_int(h), byref(stereo_params(**kw))) == SFMX_OK
 
 
 _lib = None
@@ -64,6 +86,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_stream.restype = c_void_p
         _lib.sfmx_kernel_profile_name.restype = c_char_p
         _lib.sfmx_debug_klt_slow_steps.restype = c_uint64
+        _lib.sfmx_stereo_last_us.restype = c_double
     return _lib
 
 
@@ -101,6 +124,56 @@ class Pyramid:
     def close(self):
         if self.h_:
             self.ctx.lib.sfmx_pyramid_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Stereo:
+    """Device buffers of sfmx_stereo for one (w, h, params); disparity() runs rectify -> census -> SGM -> select -> speckle."""
+
+    def __init__(self, ctx: "Context", w: int, h: int, **params):
+        self.ctx, self.w, self.h = ctx, w, h
+        self.params = stereo_params(**params)
+        self.D = self.params.num_disparities
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_stereo_create(ctx.h_, c_int(w), c_int(h), byref(self.params), byref(self.h_)))
+
+    def disparity(self, img_l, img_r, H_l, H_r, want_rect: bool = False, want_sum: bool = False):
+        """img_l / img_r: u8 [h][w] numpy arrays, or ints (device pointers of u8 [h][w] in HBM).
+        Returns disp16 int16 [h][w] (-16 invalid), or dict(disp16, rect, S) when want_rect / want_sum."""
+        on_dev = isinstance(img_l, int)
+        if on_dev != isinstance(img_r, int):
+            raise TypeError("img_l and img_r: both host arrays or both device pointers")
+        if on_dev:
+            pl, pr = c_void_p(img_l), c_void_p(img_r)
+        else:
+            img_l = np.ascontiguousarray(img_l, np.uint8)
+            img_r = np.ascontiguousarray(img_r, np.uint8)
+            assert img_l.shape == (self.h, self.w) and img_r.shape == (self.h, self.w)
+            pl, pr = _p(img_l, c_uint8), _p(img_r, c_uint8)
+        Hl, Hr = _f64(H_l).reshape(9), _f64(H_r).reshape(9)
+        d16 = np.zeros((self.h, self.w), np.int16)
+        rect = np.zeros((2, self.h, self.w), np.uint8) if want_rect else None
+        S = np.zeros((self.h, self.w, self.D), np.uint16) if want_sum else None
+        self.ctx._chk(self.ctx.lib.sfmx_stereo_disparity(self.ctx.h_, self.h_, pl, pr, c_int(1 if on_dev else 0), _p(Hl, c_double),
+                                                         _p(Hr, c_double), d16.ctypes.data_as(c_void_p),
+                                                         rect.ctypes.data_as(c_void_p) if want_rect else None,
+                                                         S.ctypes.data_as(c_void_p) if want_sum else None))
+        if want_rect or want_sum:
+            return dict(disp16=d16, rect=rect, S=S)
+        return d16
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_stereo_last_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_stereo_destroy(self.ctx.h_, self.h_)
             self.h_ = c_void_p()
 
     def __del__(self):
@@ -373,6 +446,18 @@ class Context:
         if rc not in (SFMX_OK, SFMX_ERR_SINGULAR):
             self._chk(rc)
         return rc, x
+
+    def stereo(self, w: int, h: int, **params) -> Stereo:
+        return Stereo(self, w, h, **params)
+
+    def stereo_disparity(self, img_l, img_r, H_l, H_r, want_rect: bool = False, want_sum: bool = False, **params):
+        """the device stereo stage alone on one pair (buffers created and released around the call); see Stereo.disparity"""
+        h, w = np.shape(img_l) if not isinstance(img_l, int) else params.pop("shape")
+        st = Stereo(self, w, h, **params)
+        try:
+            return st.disparity(img_l, img_r, H_l, H_r, want_rect, want_sum)
+        finally:
+            st.close()
 
     def debug_hypot(self, x, y):
         x, y = _f64(x), _f64(y)

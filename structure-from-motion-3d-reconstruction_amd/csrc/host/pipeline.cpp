@@ -3,6 +3,7 @@
 
 #include "../hip/sfmx_math.h"
 #include "cli_io.hpp"
+#include "stereo.hpp"
 #include "introsort_replay.hpp"
 #include "thread_pool.hpp"
 
@@ -2025,10 +2026,64 @@ struct sfmx_pipeline_stats {
 
 // images_host and/or images_dev: [n][h][w] u8 (images_dev = device pointer, frames already in HBM).
 // out_dir may be NULL (no files).  centres_out (optional) [n_keyframes<=cap][3].
+namespace sfmx_host {
+// the keyframe pair of sfmx_pipeline_run_ex, after the run: its frames come from the run's own source (HBM when resident)
+static void run_stereo_pair(sfmx_ctx* ctx, const MemoryFrames& src, const Mat3& K, const sfmx_stereo_request& rq, sfmx_stereo_result* out,
+                            const char* out_dir, PipelineResult& res) {
+  const int n = (int)res.kfs.size();
+  if (out) { out->n_verts = 0; out->n_faces = 0; }
+  if (n < 2) {
+    res.log += "WARN: stereo mesh export skipped (need at least 2 keyframes)\n";
+    return;
+  }
+  if (rq.kf_a < 0 || rq.kf_b < 0 || rq.kf_a >= n || rq.kf_b >= n)
+    throw SfmxFailure(SFMX_ERR_INVALID, "mesh_stereo.kf_pair (" + std::to_string(rq.kf_a) + ", " + std::to_string(rq.kf_b) +
+                                            ") out of range (keyframes=" + std::to_string(n) + ")");
+  double pose[2][12];
+  for (int v = 0; v < 2; v++) {
+    const Pose& p = res.kfs[(size_t)(v ? rq.kf_b : rq.kf_a)].pose;
+    std::memcpy(pose[v], p.R.a, 72);
+    pose[v][9] = p.t.x; pose[v][10] = p.t.y; pose[v][11] = p.t.z;
+  }
+  const size_t plane = (size_t)src.w * src.h;
+  const std::uint8_t* base = src.dev ? src.dev : src.host;
+  const std::uint8_t* ia = base + plane * (size_t)res.kfs[(size_t)rq.kf_a].frame_idx;
+  const std::uint8_t* ib = base + plane * (size_t)res.kfs[(size_t)rq.kf_b].frame_idx;
+  const int gw = (src.w + std::max(1, rq.mesh.step) - 1) / std::max(1, rq.mesh.step);
+  const int gh = (src.h + std::max(1, rq.mesh.step) - 1) / std::max(1, rq.mesh.step);
+  std::vector<double> verts((size_t)gw * gh * 3);
+  std::vector<int> faces((size_t)gw * gh * 6);
+  sfmx_stereo_result r{verts.data(), gw * gh, faces.data(), 2 * gw * gh, out ? out->disp16 : nullptr, 0, 0, {}};
+  char why[128] = {0};
+  const int rc = sfmx_host_stereo_mesh(ctx, ia, ib, src.dev ? 1 : 0, src.w, src.h, K.a, pose[0], pose[1], &rq.params, &rq.mesh, &r, why,
+                                       (int)sizeof why);
+  if (rc != SFMX_OK) throw SfmxFailure(rc, std::string("stereo mesh: ") + sfmx_last_error(ctx));
+  if (r.n_verts == 0) {
+    res.log += std::string("WARN: stereo mesh export skipped (") + why + ")\n";
+  } else if (out_dir) {
+    std::vector<V3> vv((size_t)r.n_verts);
+    for (int i = 0; i < r.n_verts; i++) vv[(size_t)i] = V3{verts[3 * (size_t)i], verts[3 * (size_t)i + 1], verts[3 * (size_t)i + 2]};
+    std::vector<std::array<int, 3>> ff((size_t)r.n_faces);
+    for (int i = 0; i < r.n_faces; i++) ff[(size_t)i] = {faces[3 * (size_t)i], faces[3 * (size_t)i + 1], faces[3 * (size_t)i + 2]};
+    write_mesh_ply((std::filesystem::path(out_dir) / ("templeRing_mesh_stereo_kf" + std::to_string(rq.kf_a) + "_kf" + std::to_string(rq.kf_b) +
+                                                     ".ply")).string(), vv, ff);
+  }
+  if (out) {
+    const int nv = std::min(r.n_verts, out->verts_cap), nf = std::min(r.n_faces, out->faces_cap);
+    if (out->verts) std::memcpy(out->verts, verts.data(), (size_t)nv * 3 * sizeof(double));
+    if (out->faces) std::memcpy(out->faces, faces.data(), (size_t)nf * 3 * sizeof(int));
+    out->n_verts = r.n_verts;
+    out->n_faces = r.n_faces;
+    out->rect = r.rect;
+  }
+}
+}  // namespace sfmx_host
+
 static int pipeline_run_body(sfmx_ctx* ctx, const std::uint8_t* images_host, const void* images_dev, int n_images, int w, int h,
                              const char* const* names, const double* K9, const double* lat, const double* lon, const std::uint8_t* has_ang,
                              const sfmx_pipeline_cfg* cfg, const char* out_dir, char* log, int log_cap, sfmx_pipeline_stats* stats,
-                             double* centres_out, int centres_cap, sfmx_host::Clock::time_point t_wall) {
+                             double* centres_out, int centres_cap, const sfmx_stereo_request* stereo, sfmx_stereo_result* stereo_out,
+                             double* kf_poses_out, int* kf_frames_out, int kf_cap, sfmx_host::Clock::time_point t_wall) {
   using namespace sfmx_host;
   try {
     MemoryFrames src;
@@ -2060,6 +2115,7 @@ static int pipeline_run_body(sfmx_ctx* ctx, const std::uint8_t* images_host, con
     const double wall = since(t_wall);
     if (std::getenv("SFMX_TRACE_PHASES")) std::fprintf(stderr, "phase %-22s %8.3f ms (since entry)\n", "run_pipeline returned", wall * 1e3);
     if (out_dir) write_outputs(out_dir, pc, meta, res);
+    if (stereo) run_stereo_pair(ctx, src, K, *stereo, stereo_out, out_dir, res);
     if (log && log_cap > 0) std::snprintf(log, (size_t)log_cap, "%s", res.log.c_str());
     if (stats) {
       const StageClock& c = res.clock;
@@ -2072,6 +2128,14 @@ static int pipeline_run_body(sfmx_ctx* ctx, const std::uint8_t* images_host, con
       for (int i = 0; i < 16; i++) { stats->us_kernel[i] = c.kernel_us[i]; stats->calls_kernel[i] = c.kernel_calls[i]; }
       stats->sec_lane_a_busy = c.lane_a_busy;
       stats->sec_lane_e_busy = c.lane_e_busy;
+    }
+    for (int k = 0; k < (int)res.kfs.size() && k < kf_cap; k++) {
+      const Keyframe& kf = res.kfs[(size_t)k];
+      if (kf_poses_out) {
+        std::memcpy(kf_poses_out + 12 * k, kf.pose.R.a, 72);
+        kf_poses_out[12 * k + 9] = kf.pose.t.x; kf_poses_out[12 * k + 10] = kf.pose.t.y; kf_poses_out[12 * k + 11] = kf.pose.t.z;
+      }
+      if (kf_frames_out) kf_frames_out[k] = kf.frame_idx;
     }
     if (centres_out)
       for (int k = 0; k < (int)res.kfs.size() && k < centres_cap; k++) {
@@ -2089,15 +2153,32 @@ static int pipeline_run_body(sfmx_ctx* ctx, const std::uint8_t* images_host, con
   }
 }
 
+int sfmx_pipeline_run_ex(sfmx_ctx* ctx, const std::uint8_t* images_host, const void* images_dev, int n_images, int w, int h,
+                         const char* const* names, const double* K9, const double* lat, const double* lon, const std::uint8_t* has_ang,
+                         const sfmx_pipeline_cfg* cfg, const char* out_dir, char* log, int log_cap, sfmx_pipeline_stats* stats,
+                         double* centres_out, int centres_cap, const sfmx_stereo_request* stereo, sfmx_stereo_result* stereo_out,
+                         double* kf_poses_out, int* kf_frames_out, int kf_cap);
 int sfmx_pipeline_run(sfmx_ctx* ctx, const std::uint8_t* images_host, const void* images_dev, int n_images, int w, int h,
                       const char* const* names, const double* K9, const double* lat, const double* lon, const std::uint8_t* has_ang,
                       const sfmx_pipeline_cfg* cfg, const char* out_dir, char* log, int log_cap, sfmx_pipeline_stats* stats,
                       double* centres_out, int centres_cap) {
+  return sfmx_pipeline_run_ex(ctx, images_host, images_dev, n_images, w, h, names, K9, lat, lon, has_ang, cfg, out_dir, log, log_cap, stats,
+                              centres_out, centres_cap, nullptr, nullptr, nullptr, nullptr, 0);
+}
+
+// sfmx_pipeline_run plus, optionally: one keyframe-pair stereo mesh computed after the run from the frames it already has
+// (stereo / stereo_out; templeRing_mesh_stereo_kf{a}_kf{b}.ply in out_dir), and every keyframe's camera->world pose
+// [n][12] (R row-major + centre) and frame index, at most kf_cap of each
+int sfmx_pipeline_run_ex(sfmx_ctx* ctx, const std::uint8_t* images_host, const void* images_dev, int n_images, int w, int h,
+                         const char* const* names, const double* K9, const double* lat, const double* lon, const std::uint8_t* has_ang,
+                         const sfmx_pipeline_cfg* cfg, const char* out_dir, char* log, int log_cap, sfmx_pipeline_stats* stats,
+                         double* centres_out, int centres_cap, const sfmx_stereo_request* stereo, sfmx_stereo_result* stereo_out,
+                         double* kf_poses_out, int* kf_frames_out, int kf_cap) {
   using namespace sfmx_host;
   if (!ctx || !cfg || !K9 || (!images_host && !images_dev) || n_images <= 0) return SFMX_ERR_INVALID;
   const auto t_wall = Clock::now();
   const int rc = pipeline_run_body(ctx, images_host, images_dev, n_images, w, h, names, K9, lat, lon, has_ang, cfg, out_dir, log, log_cap, stats,
-                                   centres_out, centres_cap, t_wall);
+                                   centres_out, centres_cap, stereo, stereo_out, kf_poses_out, kf_frames_out, kf_cap, t_wall);
   // the body's locals (map, keyframes, track histories) are gone here
   if (std::getenv("SFMX_TRACE_PHASES")) std::fprintf(stderr, "phase %-22s %8.3f ms (since entry)\n", "results released", since(t_wall) * 1e3);
   return rc;

@@ -50,6 +50,127 @@ class PipelineStats(ctypes.Structure):
         return d
 
 
+class StereoRect(ctypes.Structure):
+    _fields_ = [("R_rw", c_double * 9), ("c_left", c_double * 3), ("c_right", c_double * 3), ("f", c_double), ("cx", c_double),
+                ("cy", c_double), ("B", c_double), ("H_l", c_double * 9), ("H_r", c_double * 9), ("swapped", c_int)]
+
+    def asdict(self):
+        return dict(R_rw=np.array(self.R_rw[:]).reshape(3, 3), c_left=np.array(self.c_left[:]), c_right=np.array(self.c_right[:]),
+                    f=self.f, cx=self.cx, cy=self.cy, B=self.B, H_l=np.array(self.H_l[:]).reshape(3, 3),
+                    H_r=np.array(self.H_r[:]).reshape(3, 3), swapped=bool(self.swapped))
+
+
+class StereoMeshParams(ctypes.Structure):
+    _fields_ = [("step", c_int), ("disp_min", c_double), ("disp_jump", c_double), ("z_max_percentile", c_double)]
+
+
+class StereoRequest(ctypes.Structure):
+    _fields_ = [("kf_a", c_int), ("kf_b", c_int), ("params", capi.StereoParams), ("mesh", StereoMeshParams)]
+
+
+class StereoResult(ctypes.Structure):
+    _fields_ = [("verts", POINTER(c_double)), ("verts_cap", c_int), ("faces", POINTER(c_int)), ("faces_cap", c_int),
+                ("disp16", c_void_p), ("n_verts", c_int), ("n_faces", c_int), ("rect", StereoRect)]
+
+
+# the reference's mesh_stereo section (step, disp_min, disp_jump, z_max_percentile); disparity parameters: capi.STEREO_DEFAULTS
+STEREO_MESH_DEFAULTS = dict(step=4, disp_min=1.0, disp_jump=3.0, z_max_percentile=98.0)
+
+
+def _split_stereo_params(params: dict):
+    unknown = set(params) - set(capi.STEREO_DEFAULTS) - set(STEREO_MESH_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown stereo parameters {sorted(unknown)}")
+    sp = capi.stereo_params(**{k: v for k, v in params.items() if k in capi.STEREO_DEFAULTS})
+    mp = StereoMeshParams(**{**STEREO_MESH_DEFAULTS, **{k: v for k, v in params.items() if k in STEREO_MESH_DEFAULTS}})
+    return sp, mp
+
+
+def _pose12(pose):
+    """camera->world pose as 12 doubles (R row-major, centre): accepts a 12-array or (R, c)"""
+    if isinstance(pose, (tuple, list)) and len(pose) == 2:
+        return np.concatenate([np.asarray(pose[0], np.float64).reshape(9), np.asarray(pose[1], np.float64).reshape(3)])
+    return np.ascontiguousarray(pose, np.float64).reshape(12)
+
+
+def stereo_rectify(K, pose_a, pose_b, w: int, h: int) -> dict:
+    """Rectification of a posed pair (host, double): dict(R_rw, c_left, c_right, f, cx, cy, B, H_l, H_r, swapped).
+    Poses are camera->world (R, centre).  A zero baseline raises."""
+    lib = load_host_library()
+    K = np.ascontiguousarray(K, np.float64).reshape(9)
+    pa, pb = _pose12(pose_a), _pose12(pose_b)
+    r = StereoRect()
+    dp = POINTER(c_double)
+    rc = lib.sfmx_host_stereo_rectify(K.ctypes.data_as(dp), pa.ctypes.data_as(dp), pb.ctypes.data_as(dp), c_int(w), c_int(h), byref(r))
+    if rc != capi.SFMX_OK:
+        raise capi.SfmxError(rc, "stereo_rectify: zero baseline or degenerate pair")
+    return r.asdict()
+
+
+def _rect_struct(rect: dict) -> StereoRect:
+    r = StereoRect()
+    for k in ("R_rw", "c_left", "c_right", "H_l", "H_r"):
+        getattr(r, k)[:] = [float(v) for v in np.asarray(rect[k], np.float64).ravel()]
+    r.f, r.cx, r.cy, r.B, r.swapped = float(rect["f"]), float(rect["cx"]), float(rect["cy"]), float(rect["B"]), int(bool(rect.get("swapped")))
+    return r
+
+
+def _grid_caps(w, h, step):
+    step = max(1, int(step))
+    n = ((w + step - 1) // step) * ((h + step - 1) // step)
+    return n, 2 * n
+
+
+def stereo_grid_mesh(disp16, rect: dict, step=4, disp_min=1.0, disp_jump=3.0, z_max_percentile=98.0):
+    """The host grid mesh of a disparity map (no device): (verts [n][3], faces [m][3] int32, warn or None)."""
+    lib = load_host_library()
+    d16 = np.ascontiguousarray(disp16, np.int16)
+    h, w = d16.shape
+    vcap, fcap = _grid_caps(w, h, step)
+    verts, faces = np.zeros((vcap, 3)), np.zeros((fcap, 3), np.int32)
+    nf = c_int(0)
+    warn = ctypes.create_string_buffer(128)
+    r = _rect_struct(rect)
+    mp = StereoMeshParams(int(step), float(disp_min), float(disp_jump), float(z_max_percentile))
+    nv = lib.sfmx_host_stereo_grid_mesh(d16.ctypes.data_as(c_void_p), c_int(w), c_int(h), byref(r), byref(mp), verts.ctypes.data_as(POINTER(c_double)),
+                                        c_int(vcap), faces.ctypes.data_as(POINTER(c_int)), c_int(fcap), byref(nf), warn, c_int(len(warn)))
+    if nv < 0:
+        raise capi.SfmxError(-nv, "stereo_grid_mesh")
+    return verts[:nv].copy(), faces[:nf.value].copy(), (warn.value.decode() or None)
+
+
+def stereo_mesh(ctx: capi.Context, img_a, img_b, K, pose_a, pose_b, shape=None, **params) -> dict:
+    """Keyframe-pair stereo mesh: rectify (host) -> disparity (device) -> grid mesh (host).
+    img_a / img_b: u8 [h][w] host arrays, or device pointers (ints) with shape=(h, w).  params: capi.STEREO_DEFAULTS keys and
+    STEREO_MESH_DEFAULTS keys.  Returns dict(verts, faces, disp16 (left rectified view), swapped, rect, warn)."""
+    lib = load_host_library()
+    on_dev = isinstance(img_a, int)
+    if on_dev:
+        h, w = shape
+        pa_img, pb_img = c_void_p(img_a), c_void_p(img_b)
+    else:
+        img_a = np.ascontiguousarray(img_a, np.uint8)
+        img_b = np.ascontiguousarray(img_b, np.uint8)
+        h, w = img_a.shape
+        assert img_b.shape == (h, w)
+        pa_img, pb_img = img_a.ctypes.data_as(c_void_p), img_b.ctypes.data_as(c_void_p)
+    sp, mp = _split_stereo_params(params)
+    K = np.ascontiguousarray(K, np.float64).reshape(9)
+    pa, pb = _pose12(pose_a), _pose12(pose_b)
+    vcap, fcap = _grid_caps(w, h, mp.step)
+    verts, faces = np.zeros((vcap, 3)), np.zeros((fcap, 3), np.int32)
+    d16 = np.zeros((h, w), np.int16)
+    res = StereoResult(verts.ctypes.data_as(POINTER(c_double)), vcap, faces.ctypes.data_as(POINTER(c_int)), fcap, d16.ctypes.data_as(c_void_p))
+    warn = ctypes.create_string_buffer(128)
+    dp = POINTER(c_double)
+    rc = lib.sfmx_host_stereo_mesh(ctx.h_, pa_img, pb_img, c_int(1 if on_dev else 0), c_int(w), c_int(h), K.ctypes.data_as(dp),
+                                   pa.ctypes.data_as(dp), pb.ctypes.data_as(dp), byref(sp), byref(mp), byref(res), warn, c_int(len(warn)))
+    if rc != capi.SFMX_OK:
+        raise capi.SfmxError(rc, (ctx.lib.sfmx_last_error(ctx.h_) or b"").decode() or "stereo_mesh")
+    return dict(verts=verts[:res.n_verts].copy(), faces=faces[:res.n_faces].copy(), disp16=d16, swapped=bool(res.rect.swapped),
+                rect=res.rect.asdict(), warn=warn.value.decode() or None)
+
+
 DEFAULTS = dict(frames=12, export_pointcloud=1, max_tracks=2200, min_tracks=900, quality=0.01, min_distance=8,
                 pyr_levels=3, win_radius=5, klt_iters=10, fb_thresh=1.0, kf_min_gap=1, kf_min_inliers=200,
                 kf_parallax_px=18.0, ba_window=6, ba_iters=5, ba_max_points=600, ba_huber=3.0, ba_lambda=1e-3)
@@ -70,8 +191,12 @@ def load_host_library() -> ctypes.CDLL:
 
 
 def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=None, cfg: dict | None = None,
-        out_dir: str | None = None, images_dev: int | None = None, shape=None, timing: bool = False, comms=None):
+        out_dir: str | None = None, images_dev: int | None = None, shape=None, timing: bool = False, comms=None, stereo: dict | None = None):
     """Run the per-frame loop.  images: host [F,h,w] u8, or images_dev: device pointer with shape=(F,h,w).
+    Returns dict(log, stats, centres, kf_poses [n][12] (camera->world R row-major + centre), kf_frames [n]).
+    stereo (optional): {'kf_pair': (a, b), **params} (capi.STEREO_DEFAULTS and STEREO_MESH_DEFAULTS keys) -- after the run, the
+    stereo mesh of keyframes a and b from the run's own frames: the result gains stereo_mesh = dict(verts, faces, disp16, swapped,
+    rect), and out_dir gains templeRing_mesh_stereo_kf{a}_kf{b}.ply (a skipped export writes no file and one WARN log line).
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -94,17 +219,36 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     log = ctypes.create_string_buffer(1 << 20)
     st = PipelineStats()
     centres = np.zeros((F, 3))
+    kf_poses = np.zeros((F, 12))
+    kf_frames = np.zeros(F, np.int32)
+    req = res = None
+    if stereo is not None:
+        params = dict(stereo)
+        a, b = params.pop("kf_pair")
+        sp, mp = _split_stereo_params(params)
+        req = StereoRequest(int(a), int(b), sp, mp)
+        vcap, fcap = _grid_caps(w, h, mp.step)
+        sverts, sfaces = np.zeros((vcap, 3)), np.zeros((fcap, 3), np.int32)
+        sd16 = np.full((h, w), -16, np.int16)
+        res = StereoResult(sverts.ctypes.data_as(POINTER(c_double)), vcap, sfaces.ctypes.data_as(POINTER(c_int)), fcap, sd16.ctypes.data_as(c_void_p))
     ctx.set_timing(timing)
-    rc = lib.sfmx_pipeline_run(ctx.h_, images.ctypes.data_as(c_void_p) if images is not None else None,
-                               c_void_p(images_dev) if images_dev else None, c_int(F), c_int(w), c_int(h), arr,
-                               K.ctypes.data_as(POINTER(c_double)), lat.ctypes.data_as(POINTER(c_double)),
-                               lon.ctypes.data_as(POINTER(c_double)), has_ang.ctypes.data_as(POINTER(c_ubyte)), byref(c),
-                               out_dir.encode() if out_dir else None, log, c_int(len(log)), byref(st),
-                               centres.ctypes.data_as(POINTER(c_double)), c_int(F))
+    rc = lib.sfmx_pipeline_run_ex(ctx.h_, images.ctypes.data_as(c_void_p) if images is not None else None,
+                                  c_void_p(images_dev) if images_dev else None, c_int(F), c_int(w), c_int(h), arr,
+                                  K.ctypes.data_as(POINTER(c_double)), lat.ctypes.data_as(POINTER(c_double)),
+                                  lon.ctypes.data_as(POINTER(c_double)), has_ang.ctypes.data_as(POINTER(c_ubyte)), byref(c),
+                                  out_dir.encode() if out_dir else None, log, c_int(len(log)), byref(st),
+                                  centres.ctypes.data_as(POINTER(c_double)), c_int(F), byref(req) if req is not None else None,
+                                  byref(res) if res is not None else None, kf_poses.ctypes.data_as(POINTER(c_double)),
+                                  kf_frames.ctypes.data_as(POINTER(c_int)), c_int(F))
     text = log.value.decode()
     if rc != capi.SFMX_OK:
         raise capi.SfmxError(rc, text.strip())
-    return dict(log=text, stats=st.asdict(), centres=centres[:st.n_keyframes].copy())
+    n = st.n_keyframes
+    out = dict(log=text, stats=st.asdict(), centres=centres[:n].copy(), kf_poses=kf_poses[:n].copy(), kf_frames=kf_frames[:n].copy())
+    if res is not None:
+        out["stereo_mesh"] = dict(verts=sverts[:res.n_verts].copy(), faces=sfaces[:res.n_faces].copy(), disp16=sd16,
+                                  swapped=bool(res.rect.swapped), rect=res.rect.asdict())
+    return out
 
 
 def find_E_ransac(ctx: capi.Context, K, pi, pj, iters: int, thr: float, min_inliers: int):

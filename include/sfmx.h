@@ -274,6 +274,50 @@ int sfmx_stereo_disparity(sfmx_ctx* ctx, sfmx_stereo* st, const uint8_t* img_l, 
 /* device time (us) of the kernels of the last sfmx_stereo_disparity call when timing is on (sfmx_set_timing), else 0 */
 double sfmx_stereo_last_us(const sfmx_stereo* st);
 
+/* ---- multi-pair depth fusion: TSDF volume + marching tetrahedra ------------------------------------------ */
+/* Integration is IEEE double in one fixed expression order per view and grid point, views in the order they were added, so
+ * sum / count do not depend on how the views are batched into launches; extraction is integer scans plus one fixed double
+ * expression per vertex.  Both are bit-identical to the NumPy restatement in tests/fusion_ref.py.
+ * Grid point (i, j, k) sits at origin + (i, j, k) * voxel; arrays are [nz][ny][nx] (i fastest). */
+typedef struct sfmx_fusion sfmx_fusion;  /* device volume + pending views */
+typedef struct sfmx_fusion_params {
+  double origin[3];  /* world position of grid point (0, 0, 0); no default */
+  double voxel;      /* grid spacing, > 0; no default */
+  int nx, ny, nz;    /* grid points per axis, each >= 2, nx * ny * nz <= 2^27; no default */
+  double trunc;      /* truncation distance, >= 0 (default 0 = 4 * voxel, resolved at create) */
+  double disp_min;   /* disparities below this (pixels) are not integrated (default 1.0, the grid mesh's rule) */
+  int min_weight;    /* a grid point is defined for extraction when count >= min_weight (default 1) */
+  int max_views;     /* pending views held on the device (default 64); adding to a full stack integrates it first */
+} sfmx_fusion_params;
+/* one view: the left rectified camera of a pair (sfmx_stereo_rect: rows of R_rw are the camera axes in world coordinates,
+ * c_left its centre, f / cx / cy its pinhole, B the baseline) and the size of its disparity map */
+typedef struct sfmx_fusion_view {
+  double R_rw[9], c_left[3];
+  double f, cx, cy, B;
+  int w, h;
+} sfmx_fusion_view;
+void sfmx_fusion_default_params(sfmx_fusion_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_fusion_check_params(const sfmx_fusion_params* p);
+int sfmx_fusion_create(sfmx_ctx* ctx, const sfmx_fusion_params* p, sfmx_fusion** out);
+void sfmx_fusion_destroy(sfmx_ctx* ctx, sfmx_fusion* fu);
+/* zero sum and count, drop the pending views */
+int sfmx_fusion_reset(sfmx_ctx* ctx, sfmx_fusion* fu);
+/* queue a view: disp16 int16 [h][w] (x 16, -16 = invalid), a host pointer or (on_device = 1) a device pointer */
+int sfmx_fusion_add_view(sfmx_ctx* ctx, sfmx_fusion* fu, const sfmx_fusion_view* view, const int16_t* disp16, int on_device);
+/* queue a view whose disparity is the last map sfmx_stereo_disparity computed on st (copied device to device) */
+int sfmx_fusion_add_stereo_view(sfmx_ctx* ctx, sfmx_fusion* fu, const sfmx_fusion_view* view, const sfmx_stereo* st);
+/* integrate every pending view in one launch */
+int sfmx_fusion_integrate(sfmx_ctx* ctx, sfmx_fusion* fu);
+/* integrates the pending views, then sum (double) / count (int32) [nz][ny][nx] to the host; either may be NULL */
+int sfmx_fusion_read(sfmx_ctx* ctx, sfmx_fusion* fu, double* sum, int32_t* count);
+/* integrates the pending views, then extracts the surface: verts double [n][3], faces int32 [m][3].  n_verts / n_faces are
+ * always set; with verts and faces NULL only the counts are computed; caps below the counts give SFMX_ERR_INVALID. */
+int sfmx_fusion_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts_cap, int32_t* faces, int faces_cap, int* n_verts,
+                        int* n_faces);
+/* device time (us) of the last sfmx_fusion_integrate / _extract when timing is on (sfmx_set_timing), else 0 */
+double sfmx_fusion_last_us(const sfmx_fusion* fu);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

@@ -32,6 +32,9 @@ SYMBOLS = [
     "sfmx_debug_hypot", "sfmx_debug_divsqrt", "sfmx_debug_klt_slow_steps",
     "sfmx_stereo_default_params", "sfmx_stereo_check_params", "sfmx_stereo_create", "sfmx_stereo_destroy", "sfmx_stereo_disparity",
     "sfmx_stereo_last_us",
+    "sfmx_fusion_default_params", "sfmx_fusion_check_params", "sfmx_fusion_create", "sfmx_fusion_destroy", "sfmx_fusion_reset",
+    "sfmx_fusion_add_view", "sfmx_fusion_add_stereo_view", "sfmx_fusion_integrate", "sfmx_fusion_read", "sfmx_fusion_extract",
+    "sfmx_fusion_last_us",
 ]
 
 
@@ -58,6 +61,56 @@ def stereo_params(**kw) -> StereoParams:
     if unknown:
         raise TypeError(f"unknown stereo parameters {sorted(unknown)}")
     return StereoParams(**{**STEREO_DEFAULTS, **kw})
+
+
+class FusionParams(ctypes.Structure):
+    _fields_ = [("origin", c_double * 3), ("voxel", c_double), ("nx", c_int), ("ny", c_int), ("nz", c_int), ("trunc", c_double),
+                ("disp_min", c_double), ("min_weight", c_int), ("max_views", c_int)]
+
+
+class FusionView(ctypes.Structure):
+    _fields_ = [("R_rw", c_double * 9), ("c_left", c_double * 3), ("f", c_double), ("cx", c_double), ("cy", c_double), ("B", c_double),
+                ("w", c_int), ("h", c_int)]
+
+
+# trunc 0 = 4 x voxel (resolved at create); the volume (origin, voxel, dims) has no default
+FUSION_DEFAULTS = dict(trunc=0.0, disp_min=1.0, min_weight=1, max_views=64)
+
+
+def fusion_params(origin=(0.0, 0.0, 0.0), voxel=0.0, dims=(0, 0, 0), **kw) -> FusionParams:
+    unknown = set(kw) - set(FUSION_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown fusion parameters {sorted(unknown)}")
+    p = FusionParams()
+    p.origin[:] = [float(v) for v in origin]
+    p.voxel = float(voxel)
+    p.nx, p.ny, p.nz = (int(v) for v in dims)
+    for k, v in {**FUSION_DEFAULTS, **kw}.items():
+        setattr(p, k, v)
+    return p
+
+
+def fusion_default_params() -> dict:
+    """sfmx_fusion_default_params as a dict (needs no device)"""
+    p = FusionParams()
+    load_library().sfmx_fusion_default_params(byref(p))
+    return dict(origin=tuple(p.origin), voxel=p.voxel, dims=(p.nx, p.ny, p.nz), trunc=p.trunc, disp_min=p.disp_min,
+                min_weight=p.min_weight, max_views=p.max_views)
+
+
+def fusion_check_params(**kw) -> bool:
+    """True if sfmx_fusion_create would accept the volume and parameters; needs no device"""
+    return load_library().sfmx_fusion_check_params(byref(fusion_params(**kw))) == SFMX_OK
+
+
+def fusion_view(cam: dict, w: int, h: int) -> FusionView:
+    """cam: a rectified left camera, dict(R_rw, c_left, f, cx, cy, B) (e.g. pipeline.stereo_rectify's result)"""
+    v = FusionView()
+    v.R_rw[:] = [float(x) for x in np.asarray(cam["R_rw"], np.float64).ravel()]
+    v.c_left[:] = [float(x) for x in np.asarray(cam["c_left"], np.float64).ravel()]
+    v.f, v.cx, v.cy, v.B = float(cam["f"]), float(cam["cx"]), float(cam["cy"]), float(cam["B"])
+    v.w, v.h = int(w), int(h)
+    return v
 
 
 def stereo_check_params(w: int, h: int, **kw) -> bool:
@@ -87,6 +140,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_kernel_profile_name.restype = c_char_p
         _lib.sfmx_debug_klt_slow_steps.restype = c_uint64
         _lib.sfmx_stereo_last_us.restype = c_double
+        _lib.sfmx_fusion_last_us.restype = c_double
     return _lib
 
 
@@ -124,6 +178,82 @@ class Pyramid:
     def close(self):
         if self.h_:
             self.ctx.lib.sfmx_pyramid_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Fusion:
+    """sfmx_fusion: a TSDF volume of dims = (nx, ny, nz) grid points at origin + (i, j, k) * voxel, plus its pending views."""
+
+    def __init__(self, ctx: "Context", origin, voxel, dims, **params):
+        self.ctx = ctx
+        self.params = fusion_params(origin, voxel, dims, **params)
+        self.dims = tuple(int(v) for v in dims)
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_fusion_create(ctx.h_, byref(self.params), byref(self.h_)))
+
+    def add_view(self, cam: dict, disp16, shape=None):
+        """disp16: int16 [h][w] numpy array, or an int (device pointer) with shape=(h, w)"""
+        if isinstance(disp16, int):
+            h, w = shape
+            ptr, on_dev = c_void_p(disp16), 1
+        else:
+            disp16 = np.ascontiguousarray(disp16, np.int16)
+            h, w = disp16.shape
+            ptr, on_dev = disp16.ctypes.data_as(c_void_p), 0
+        v = fusion_view(cam, w, h)
+        self.ctx._chk(self.ctx.lib.sfmx_fusion_add_view(self.ctx.h_, self.h_, byref(v), ptr, c_int(on_dev)))
+
+    def add_stereo_view(self, cam: dict, st: Stereo):
+        """the last disparity map st computed, copied on the device"""
+        v = fusion_view(cam, st.w, st.h)
+        self.ctx._chk(self.ctx.lib.sfmx_fusion_add_stereo_view(self.ctx.h_, self.h_, byref(v), st.h_))
+
+    def integrate(self):
+        self.ctx._chk(self.ctx.lib.sfmx_fusion_integrate(self.ctx.h_, self.h_))
+
+    def reset(self):
+        self.ctx._chk(self.ctx.lib.sfmx_fusion_reset(self.ctx.h_, self.h_))
+
+    def read(self):
+        """(sum float64, count int32), both [nz][ny][nx]; integrates the pending views first"""
+        nx, ny, nz = self.dims
+        s, c = np.zeros((nz, ny, nx)), np.zeros((nz, ny, nx), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_fusion_read(self.ctx.h_, self.h_, _p(s, c_double), _p(c, c_int32)))
+        return s, c
+
+    def counts(self):
+        """(n_verts, n_faces) of the surface, without the arrays"""
+        nv, nf = c_int(0), c_int(0)
+        self.ctx._chk(self.ctx.lib.sfmx_fusion_extract(self.ctx.h_, self.h_, None, c_int(0), None, c_int(0), byref(nv), byref(nf)))
+        return nv.value, nf.value
+
+    def extract_into(self, verts_cap: int, faces_cap: int):
+        """the raw call with caller-chosen caps: (status, verts, faces, n_verts, n_faces); arrays sized by the caps"""
+        verts, faces = np.zeros((max(verts_cap, 1), 3)), np.zeros((max(faces_cap, 1), 3), np.int32)
+        nv, nf = c_int(0), c_int(0)
+        rc = self.ctx.lib.sfmx_fusion_extract(self.ctx.h_, self.h_, _p(verts, c_double), c_int(verts_cap), _p(faces, c_int32),
+                                              c_int(faces_cap), byref(nv), byref(nf))
+        return rc, verts, faces, nv.value, nf.value
+
+    def extract(self):
+        """(verts float64 [n][3], faces int32 [m][3]); integrates the pending views first"""
+        nv, nf = self.counts()
+        rc, verts, faces, nv, nf = self.extract_into(nv, nf)
+        self.ctx._chk(rc)
+        return verts[:nv].copy(), faces[:nf].copy()
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_fusion_last_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_fusion_destroy(self.ctx.h_, self.h_)
             self.h_ = c_void_p()
 
     def __del__(self):
@@ -446,6 +576,9 @@ class Context:
         if rc not in (SFMX_OK, SFMX_ERR_SINGULAR):
             self._chk(rc)
         return rc, x
+
+    def fusion(self, origin, voxel, dims, **params) -> "Fusion":
+        return Fusion(self, origin, voxel, dims, **params)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

@@ -143,6 +143,7 @@ static inline PyrDesc make_desc(const sfmx_pyramid* p) {
 int sfmx_fail(sfmx_ctx* ctx, int status, const char* what, hipError_t e);
 int sfmx_pyramid_settle(sfmx_ctx* ctx, const sfmx_pyramid* pyr);  // image.hip: order the main stream behind an asynchronous build
 extern "C" void sfmx_release_graphs(sfmx_ctx* ctx);  // image.hip: drop the hipGraph executables cached for this context
+const int16_t* sfmx_stereo_device_disp16(const sfmx_stereo* st, int* w, int* h);  // stereo.hip: the last disparity map on the device
 
 #define SFMX_HIP(ctx, call)                                                         \
   do {                                                                              \

@@ -295,6 +295,12 @@ struct sfmx_stereo {
   double last_us = 0.0;
 };
 
+const int16_t* sfmx_stereo_device_disp16(const sfmx_stereo* st, int* w, int* h) {
+  *w = st->w;
+  *h = st->h;
+  return st->d16;
+}
+
 extern "C" {
 
 void sfmx_stereo_default_params(sfmx_stereo_params* p) {

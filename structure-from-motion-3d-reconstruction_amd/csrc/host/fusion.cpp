@@ -1,0 +1,147 @@
+// fusion.cpp — multi-pair depth fusion on the host: for each pair, rectify (host), disparity (device) and queue the left
+// rectified view with its device disparity map; then one integration and one extraction.
+#include "fusion.hpp"
+
+#include <array>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "pipeline.hpp"
+#include "stereo.hpp"
+
+// Weak: a libsfmx.so without the device stages (tests/fake_sfmx, the CPU stand-in of the sanitizer builds) still links;
+// sfmx_host_fusion_mesh then reports SFMX_ERR_UNSUPPORTED.
+#pragma weak sfmx_stereo_check_params
+#pragma weak sfmx_stereo_create
+#pragma weak sfmx_stereo_destroy
+#pragma weak sfmx_stereo_disparity
+#pragma weak sfmx_fusion_check_params
+#pragma weak sfmx_fusion_create
+#pragma weak sfmx_fusion_destroy
+#pragma weak sfmx_fusion_add_stereo_view
+#pragma weak sfmx_fusion_integrate
+#pragma weak sfmx_fusion_extract
+
+namespace {
+
+struct Guard {
+  sfmx_ctx* ctx;
+  sfmx_stereo* st = nullptr;
+  sfmx_fusion* fu = nullptr;
+  ~Guard() {
+    if (st) sfmx_stereo_destroy(ctx, st);
+    if (fu) sfmx_fusion_destroy(ctx, fu);
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+void sfmx_host_fusion_free(sfmx_fusion_result* res) {
+  if (!res) return;
+  std::free(res->verts);
+  std::free(res->faces);
+  res->verts = nullptr;
+  res->faces = nullptr;
+  res->n_verts = res->n_faces = 0;
+}
+
+int sfmx_host_fusion_mesh(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                          const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp, const sfmx_fusion_params* fp,
+                          sfmx_fusion_result* res, const char* ply_path, char* warn, int warn_cap) {
+  if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
+    return SFMX_ERR_INVALID;
+  *res = sfmx_fusion_result{};
+  if (warn && warn_cap > 0) warn[0] = 0;
+  if (!&sfmx_fusion_create || !&sfmx_stereo_disparity) return SFMX_ERR_UNSUPPORTED;
+  int rc = sfmx_stereo_check_params(w, h, sp);
+  if (rc != SFMX_OK) return rc;
+  rc = sfmx_fusion_check_params(fp);
+  if (rc != SFMX_OK) return rc;
+  std::string log;
+  Guard g{ctx};
+  rc = sfmx_fusion_create(ctx, fp, &g.fu);
+  if (rc != SFMX_OK) return rc;
+  std::vector<int16_t> d16((size_t)w * h);  // sfmx_stereo_disparity always returns the map to the host
+  for (int q = 0; q < m; q++) {
+    const int a = pairs[2 * q], b = pairs[2 * q + 1];
+    const std::string tag = "(" + std::to_string(a) + ", " + std::to_string(b) + ")";
+    if (a < 0 || a >= n || b < 0 || b >= n) {
+      log += "WARN: fusion pair " + tag + " skipped (out of range, images=" + std::to_string(n) + ")\n";
+      continue;
+    }
+    sfmx_stereo_rect r{};
+    if (sfmx_host_stereo_rectify(K9, poses12 + 12 * a, poses12 + 12 * b, w, h, &r) != SFMX_OK) {
+      // rectification fails on a zero (or non-finite) baseline, or when the rectified y axis degenerates (both optical
+      // axes parallel to the baseline)
+      const double* ca = poses12 + 12 * a + 9;
+      const double* cb = poses12 + 12 * b + 9;
+      const bool same = ca[0] == cb[0] && ca[1] == cb[1] && ca[2] == cb[2];
+      log += "WARN: fusion pair " + tag + (same ? " skipped (zero baseline)\n" : " skipped (degenerate rectification)\n");
+      continue;
+    }
+    if (!g.st) {
+      rc = sfmx_stereo_create(ctx, w, h, sp, &g.st);
+      if (rc != SFMX_OK) return rc;
+    }
+    const uint8_t* il = r.swapped ? images[b] : images[a];
+    const uint8_t* ir = r.swapped ? images[a] : images[b];
+    rc = sfmx_stereo_disparity(ctx, g.st, il, ir, on_device, r.H_l, r.H_r, d16.data(), nullptr, nullptr);
+    if (rc != SFMX_OK) return rc;
+    sfmx_fusion_view v{};
+    std::memcpy(v.R_rw, r.R_rw, sizeof v.R_rw);
+    std::memcpy(v.c_left, r.c_left, sizeof v.c_left);
+    v.f = r.f;
+    v.cx = r.cx;
+    v.cy = r.cy;
+    v.B = r.B;
+    v.w = w;
+    v.h = h;
+    rc = sfmx_fusion_add_stereo_view(ctx, g.fu, &v, g.st);
+    if (rc != SFMX_OK) return rc;
+    res->n_views++;
+  }
+  rc = sfmx_fusion_integrate(ctx, g.fu);
+  if (rc != SFMX_OK) return rc;
+  int nv = 0, nf = 0;
+  rc = sfmx_fusion_extract(ctx, g.fu, nullptr, 0, nullptr, 0, &nv, &nf);
+  if (rc != SFMX_OK) return rc;
+  if (nf > 0) {
+    res->verts = static_cast<double*>(std::malloc((size_t)nv * 3 * sizeof(double)));
+    res->faces = static_cast<int32_t*>(std::malloc((size_t)nf * 3 * sizeof(int32_t)));
+    if (!res->verts || !res->faces) {
+      sfmx_host_fusion_free(res);
+      return SFMX_ERR_INVALID;
+    }
+    rc = sfmx_fusion_extract(ctx, g.fu, res->verts, nv, res->faces, nf, &nv, &nf);
+    if (rc != SFMX_OK) {
+      sfmx_host_fusion_free(res);
+      return rc;
+    }
+    res->n_verts = nv;
+    res->n_faces = nf;
+  }
+  if (ply_path) {
+    if (nf == 0) {
+      log += "WARN: fused mesh export skipped (no faces)\n";
+    } else {
+      std::vector<sfmx_host::V3> vv((size_t)nv);
+      for (int i = 0; i < nv; i++) vv[(size_t)i] = sfmx_host::V3{res->verts[3 * i], res->verts[3 * i + 1], res->verts[3 * i + 2]};
+      std::vector<std::array<int, 3>> ff((size_t)nf);
+      for (int i = 0; i < nf; i++) ff[(size_t)i] = {res->faces[3 * i], res->faces[3 * i + 1], res->faces[3 * i + 2]};
+      try {
+        sfmx_host::write_mesh_ply(ply_path, vv, ff);
+      } catch (const std::exception& e) {
+        log += std::string("WARN: fused mesh export failed (") + e.what() + ")\n";
+      }
+    }
+  }
+  if (warn && warn_cap > 0) std::snprintf(warn, (size_t)warn_cap, "%s", log.c_str());
+  return SFMX_OK;
+}
+
+}  // extern "C"

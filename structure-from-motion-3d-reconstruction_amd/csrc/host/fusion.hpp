@@ -1,0 +1,26 @@
+// fusion.hpp — host side of multi-pair depth fusion (fusion.cpp): every listed keyframe pair through rectification and the
+// device disparity into one TSDF volume (sfmx_fusion_*), then one surface.  C structs: bound by pipeline.py through ctypes.
+#pragma once
+#include <cstdint>
+
+#include "../../../include/sfmx.h"
+
+extern "C" {
+
+// outputs of sfmx_host_fusion_mesh, allocated by the library (release with sfmx_host_fusion_free):
+// verts double [n_verts][3], faces int32 [n_faces][3]; n_views = pairs integrated (skipped ones not counted)
+struct sfmx_fusion_result {
+  double* verts;
+  int32_t* faces;
+  int n_verts, n_faces, n_views;
+};
+
+// images: n pointers to u8 [h][w] (host, or device with on_device = 1); poses12 [n][12] camera->world R (row-major) + centre;
+// pairs [m][2] indices into images.  A pair out of range or that cannot be rectified (zero baseline, degenerate
+// rectified axes) is skipped with one WARN line in warn.
+// ply_path (optional): the surface as PLY (not written when it has no faces; a WARN line says so).
+int sfmx_host_fusion_mesh(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                          const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp, const sfmx_fusion_params* fp,
+                          sfmx_fusion_result* res, const char* ply_path, char* warn, int warn_cap);
+void sfmx_host_fusion_free(sfmx_fusion_result* res);
+}

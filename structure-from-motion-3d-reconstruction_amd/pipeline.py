@@ -171,6 +171,58 @@ def stereo_mesh(ctx: capi.Context, img_a, img_b, K, pose_a, pose_b, shape=None, 
                 rect=res.rect.asdict(), warn=warn.value.decode() or None)
 
 
+class FusionResult(ctypes.Structure):
+    _fields_ = [("verts", POINTER(c_double)), ("faces", POINTER(c_int)), ("n_verts", c_int), ("n_faces", c_int), ("n_views", c_int)]
+
+
+def _split_fusion_params(params: dict):
+    unknown = set(params) - set(capi.STEREO_DEFAULTS) - set(capi.FUSION_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown fusion parameters {sorted(unknown)}")
+    sp = capi.stereo_params(**{k: v for k, v in params.items() if k in capi.STEREO_DEFAULTS})
+    return sp, {k: v for k, v in params.items() if k in capi.FUSION_DEFAULTS}
+
+
+def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, **params) -> dict:
+    """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
+    the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
+    poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
+    explicit: dims = (nx, ny, nz) grid points at origin + (i, j, k) * voxel.  params: capi.STEREO_DEFAULTS and
+    capi.FUSION_DEFAULTS keys.  Returns dict(verts, faces, views (pairs integrated), warn (WARN lines or None))."""
+    lib = load_host_library()
+    if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
+        h, w = shape
+        n = len(images)
+        ptrs = (c_void_p * max(n, 1))(*images)
+        on_dev, keep = 1, None
+    else:
+        keep = np.ascontiguousarray(images, np.uint8)
+        n, h, w = keep.shape
+        ptrs = (c_void_p * max(n, 1))(*[keep[i].ctypes.data for i in range(n)])
+        on_dev = 0
+    poses12 = np.ascontiguousarray(np.stack([_pose12(p) for p in poses]) if len(poses) else np.zeros((0, 12)), np.float64)
+    if len(poses12) != n:
+        raise ValueError(f"{n} images but {len(poses12)} poses")
+    pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    sp, fkw = _split_fusion_params(params)
+    fp = capi.fusion_params(origin, voxel, dims, **fkw)
+    K = np.ascontiguousarray(K, np.float64).reshape(9)
+    res = FusionResult()
+    warn = ctypes.create_string_buffer(1 << 16)
+    dp = POINTER(c_double)
+    rc = lib.sfmx_host_fusion_mesh(ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp),
+                                   poses12.ctypes.data_as(dp), pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp),
+                                   byref(res), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
+    if rc != capi.SFMX_OK:
+        raise capi.SfmxError(rc, (ctx.lib.sfmx_last_error(ctx.h_) or b"").decode() or "fuse")
+    try:
+        verts = np.ctypeslib.as_array(res.verts, (res.n_verts, 3)).copy() if res.n_faces else np.zeros((0, 3))
+        faces = np.ctypeslib.as_array(res.faces, (res.n_faces, 3)).astype(np.int32) if res.n_faces else np.zeros((0, 3), np.int32)
+    finally:
+        lib.sfmx_host_fusion_free(byref(res))
+    return dict(verts=verts, faces=faces, views=int(res.n_views), warn=warn.value.decode() or None)
+
+
 DEFAULTS = dict(frames=12, export_pointcloud=1, max_tracks=2200, min_tracks=900, quality=0.01, min_distance=8,
                 pyr_levels=3, win_radius=5, klt_iters=10, fb_thresh=1.0, kf_min_gap=1, kf_min_inliers=200,
                 kf_parallax_px=18.0, ba_window=6, ba_iters=5, ba_max_points=600, ba_huber=3.0, ba_lambda=1e-3)
@@ -191,12 +243,16 @@ def load_host_library() -> ctypes.CDLL:
 
 
 def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=None, cfg: dict | None = None,
-        out_dir: str | None = None, images_dev: int | None = None, shape=None, timing: bool = False, comms=None, stereo: dict | None = None):
+        out_dir: str | None = None, images_dev: int | None = None, shape=None, timing: bool = False, comms=None, stereo: dict | None = None,
+        fusion: dict | None = None):
     """Run the per-frame loop.  images: host [F,h,w] u8, or images_dev: device pointer with shape=(F,h,w).
     Returns dict(log, stats, centres, kf_poses [n][12] (camera->world R row-major + centre), kf_frames [n]).
     stereo (optional): {'kf_pair': (a, b), **params} (capi.STEREO_DEFAULTS and STEREO_MESH_DEFAULTS keys) -- after the run, the
     stereo mesh of keyframes a and b from the run's own frames: the result gains stereo_mesh = dict(verts, faces, disp16, swapped,
     rect), and out_dir gains templeRing_mesh_stereo_kf{a}_kf{b}.ply (a skipped export writes no file and one WARN log line).
+    fusion (optional): {'pairs': [(a, b), ...], 'origin', 'voxel', 'dims', **params} (keyframe indices; params as fuse) -- after
+    the run, fuse() on the run's own keyframe frames and kf_poses: the result gains fused_mesh = fuse()'s dict, and out_dir
+    gains templeRing_mesh_fused.ply.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -248,6 +304,16 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     if res is not None:
         out["stereo_mesh"] = dict(verts=sverts[:res.n_verts].copy(), faces=sfaces[:res.n_faces].copy(), disp16=sd16,
                                   swapped=bool(res.rect.swapped), rect=res.rect.asdict())
+    if fusion is not None:
+        fz = dict(fusion)
+        pairs, origin, voxel, dims = fz.pop("pairs"), fz.pop("origin"), fz.pop("voxel"), fz.pop("dims")
+        frames = [int(f) for f in out["kf_frames"]]
+        if images is not None:
+            imgs, fshape = images[frames], None
+        else:
+            imgs, fshape = [int(images_dev) + f * h * w for f in frames], (h, w)
+        ply = os.path.join(out_dir, "templeRing_mesh_fused.ply") if out_dir else None
+        out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply, **fz)
     return out
 
 

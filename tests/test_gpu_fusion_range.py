@@ -1,0 +1,111 @@
+"""GPU suite: the fusion kernels over their whole parameter range (sfmx_fusion_check_params), sum bits, count, vertex bits and
+faces against the NumPy restatement (tests/fusion_ref.py): a noise slab that reaches every (tetrahedron, case) row of the
+triangle table and shares vertices between cells, volume shapes around the 64 x 4 blocks of the integration and the 1 024-element
+blocks of the scans (up to 1 024^2 grid points and one slice more), trunc / disp_min / min_weight away from their defaults, maps
+holding 0, -1, -32768 and 32767, views of different sizes in one volume (the stack regrown after use), and cameras inside,
+behind and partly beside the volume.  The inputs come from tests/range_inputs.py; tests/test_range_inputs_cpu.py asserts that
+they hold what these cases rely on."""
+import importlib
+
+import numpy as np
+import pytest
+
+import helpers as H
+import range_inputs as RI
+from test_gpu_fusion import _check
+
+pytestmark = pytest.mark.gpu
+capi = importlib.import_module(H.PKG_NAME + ".capi")
+VOL, TRUNC = RI.SLAB_VOL, RI.SLAB_TRUNC
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = capi.Context(0)
+    yield c
+    c.close()
+
+
+def _case(ctx, vol, views, what, **params):
+    """all views into one volume, then every output against the reference on the same order of views"""
+    ref_kw = {k: v for k, v in params.items() if k != "max_views"}
+    ref = RI.fuse_ref(vol, views, **ref_kw)
+    fu = ctx.fusion(**vol, **params)
+    for cam, d16 in views:
+        fu.add_view(cam, d16)
+    _check(fu, ref, what)
+    n = (len(ref["verts"]), len(ref["faces"]))
+    assert fu.counts() == n
+    fu.close()
+    return ref
+
+
+def test_slab_reaches_every_table_row(ctx):
+    views = [RI.slab_view(**VOL)]
+    ref = RI.fuse_ref(VOL, views, trunc=TRUNC)
+    configs, pairs = RI.table_coverage(ref["sum"], ref["count"])
+    assert len(pairs) == 96 and len(configs) >= 250, (len(pairs), len(configs))  # a property of the input, before the device
+    _case(ctx, VOL, views, "noise slab", trunc=TRUNC)
+
+
+@pytest.mark.parametrize("name", list(RI.BLOCK_SHAPES))
+def test_volume_shapes_at_block_boundaries(ctx, name):
+    vol, views, trunc = RI.shape_case(*RI.BLOCK_SHAPES[name])
+    ref = _case(ctx, vol, views, name, trunc=trunc)
+    assert len(ref["faces"]) > 500
+
+
+@pytest.mark.parametrize("name", list(RI.BIG_SHAPES))
+def test_volume_shapes_at_scan_level_boundary(ctx, name):
+    """1 024^2 grid points (the second scan level exactly full) and one slice more; millions of vertices and faces"""
+    vol, views, trunc = RI.shape_case(*RI.BIG_SHAPES[name])
+    ref = _case(ctx, vol, views, name, trunc=trunc)
+    assert len(ref["faces"]) > 10 ** 6
+
+
+@pytest.fixture(scope="module")
+def views3():
+    return RI.slab_views3(extra=(-1, -32768, 32767))
+
+
+@pytest.mark.parametrize("trunc", [0.0, 0.5 * VOL["voxel"], TRUNC])
+def test_trunc(ctx, views3, trunc):
+    ref = _case(ctx, VOL, views3, f"trunc {trunc}", trunc=trunc)
+    assert len(ref["faces"]) > 1000
+
+
+@pytest.mark.parametrize("disp_min", [-5.0, 0.0, 1.0, 40.0, 57.0, float("inf")])
+def test_disp_min(ctx, views3, disp_min):
+    """disp_min <= 0 lets a disparity of 0 through: Z = +inf, a contribution of exactly 1.0 and no non-finite value anywhere"""
+    ref = _case(ctx, VOL, views3, f"disp_min {disp_min}", trunc=TRUNC, disp_min=disp_min)
+    assert np.isfinite(ref["sum"]).all() and np.isfinite(ref["verts"]).all()
+    assert (len(ref["faces"]) == 0) == (disp_min == float("inf"))
+
+
+@pytest.mark.parametrize("min_weight", [1, 2, 3, 4])
+def test_min_weight(ctx, views3, min_weight):
+    """three views: min_weight 4 = views + 1 is the empty surface, (0, 3) shaped outputs and counts (0, 0)"""
+    ref = _case(ctx, VOL, views3, f"min_weight {min_weight}", trunc=TRUNC, min_weight=min_weight)
+    assert (len(ref["faces"]) == 0) == (min_weight == 4)
+
+
+@pytest.mark.parametrize("max_views", [1, 2, 64])
+@pytest.mark.parametrize("order", ["small_first", "reversed"])
+def test_views_of_different_sizes(ctx, order, max_views):
+    """40 x 30, 640 x 480, 320 x 240 and the reverse: a larger map arrives after smaller ones have used the stack"""
+    views = RI.mixed_size_views()
+    if order == "reversed":
+        views = views[::-1]
+    ref = _case(ctx, VOL, views, f"{order}, max_views {max_views}", trunc=TRUNC, max_views=max_views)
+    assert len(ref["faces"]) > 10000
+
+
+def test_cameras_inside_behind_and_beside(ctx):
+    """q2 <= 0 for half of the grid points (camera inside), for all of them (camera looking away), and an image whose four
+    borders cut through the volume (the floor(u + 0.5) bounds on both sides); each alone, then all with a plain slab view"""
+    special = dict(inside=RI.inside_view(), away=RI.away_view(), border=RI.border_view())
+    for name, view in special.items():
+        ref = _case(ctx, VOL, [view], name, trunc=TRUNC)
+        assert ref["count"].any() == (name != "away")
+    ref = _case(ctx, VOL, [RI.slab_view(**VOL, seed=1)] + list(special.values()), "all four", trunc=TRUNC)
+    assert len(ref["faces"]) > 10000

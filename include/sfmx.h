@@ -318,6 +318,56 @@ int sfmx_fusion_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts
 /* device time (us) of the last sfmx_fusion_integrate / _extract when timing is on (sfmx_set_timing), else 0 */
 double sfmx_fusion_last_us(const sfmx_fusion* fu);
 
+/* ---- appearance of the fused surface: vertex normals and multi-view vertex intensity ---------------------- */
+/* Normals are the normalised gradient of the volume's signed distance (central differences, one-sided next to undefined grid
+ * points), interpolated along each vertex's edge with the extraction's own t; they point out of the surface.  Intensity is
+ * the rounded mean of the rectified left images over the views that see the vertex: it faces the camera (cull) and the view's
+ * own depth at its pixel agrees with the vertex's within depth_tol.  The projection is the integration's, everything after
+ * the depth test is integer, so both are bit-identical to the NumPy restatement in tests/appearance_ref.py. */
+/* sfmx_fusion_extract with normals: the same verts and faces bit for bit, plus normals double [n][3] in vertex order (zero
+ * where the gradient vanishes).  With verts, faces and normals NULL only the counts are computed; otherwise all three are
+ * required.  The vertices and normals stay on the device inside fu for sfmx_shade_fusion until the volume changes
+ * (integrate, reset) or sfmx_fusion_extract overwrites them. */
+int sfmx_fusion_extract_normals(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts_cap, int32_t* faces, int faces_cap,
+                                double* normals, int* n_verts, int* n_faces);
+/* device time (us) of the normals kernel of the last sfmx_fusion_extract_normals when timing is on, else 0 (it is also part
+ * of sfmx_fusion_last_us) */
+double sfmx_fusion_normals_us(const sfmx_fusion* fu);
+
+typedef struct sfmx_shade sfmx_shade;  /* retained views: camera, disparity map and left rectified image, on the device */
+typedef struct sfmx_shade_params {
+  double depth_tol;  /* a view sees a vertex when |Z(view pixel) - depth of the vertex| <= depth_tol; > 0; no default */
+  double disp_min;   /* disparities below this (pixels) are not used (default 1.0) */
+  int cull;          /* 1 (default): only views the vertex's normal faces, n . (X - c_left) < 0; 0: off */
+  int fill;          /* grey of a vertex no view sees, 0..255 (default 0) */
+} sfmx_shade_params;
+void sfmx_shade_default_params(sfmx_shade_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_shade_check_params(const sfmx_shade_params* p);
+int sfmx_shade_create(sfmx_ctx* ctx, sfmx_shade** out);
+void sfmx_shade_destroy(sfmx_ctx* ctx, sfmx_shade* sh);
+/* drop every view (the device memory is kept for the next ones) */
+int sfmx_shade_reset(sfmx_ctx* ctx, sfmx_shade* sh);
+/* append a view: disp16 int16 [h][w] (x 16, -16 = invalid) and its left rectified image u8 [h][w], both host pointers or
+ * (on_device = 1) both device pointers; copied (3 bytes per pixel, kept until reset / destroy).  Views of different sizes
+ * may be mixed; w <= 4096.  There is no view limit: the storage grows. */
+int sfmx_shade_add_view(sfmx_ctx* ctx, sfmx_shade* sh, const sfmx_fusion_view* view, const int16_t* disp16, const uint8_t* image,
+                        int on_device);
+/* append the last disparity map and left rectified image sfmx_stereo_disparity computed on st (copied device to device) */
+int sfmx_shade_add_stereo_view(sfmx_ctx* ctx, sfmx_shade* sh, const sfmx_fusion_view* view, const sfmx_stereo* st);
+int sfmx_shade_view_count(const sfmx_shade* sh);
+/* verts / normals double [n][3], host pointers or (on_device = 1) device pointers; normals may be NULL only with cull = 0.
+ * grey_out u8 [n] and views_out int32 [n] (the number of views that saw the vertex) on the host; either may be NULL.
+ * n = 0 or no views is not an error (every vertex gets fill and 0). */
+int sfmx_shade_vertices(sfmx_ctx* ctx, sfmx_shade* sh, const double* verts, const double* normals, int n, int on_device,
+                        const sfmx_shade_params* p, uint8_t* grey_out, int32_t* views_out);
+/* the same for the vertices and normals the last sfmx_fusion_extract_normals left on the device inside fu (no host round
+ * trip); SFMX_ERR_INVALID when fu holds none.  grey_out / views_out are sized by that call's n_verts. */
+int sfmx_shade_fusion(sfmx_ctx* ctx, sfmx_shade* sh, const sfmx_fusion* fu, const sfmx_shade_params* p, uint8_t* grey_out,
+                      int32_t* views_out);
+/* device time (us) of the kernel of the last sfmx_shade_vertices / _fusion when timing is on (sfmx_set_timing), else 0 */
+double sfmx_shade_last_us(const sfmx_shade* sh);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

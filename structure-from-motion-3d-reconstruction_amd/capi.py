@@ -35,6 +35,10 @@ SYMBOLS = [
     "sfmx_fusion_default_params", "sfmx_fusion_check_params", "sfmx_fusion_create", "sfmx_fusion_destroy", "sfmx_fusion_reset",
     "sfmx_fusion_add_view", "sfmx_fusion_add_stereo_view", "sfmx_fusion_integrate", "sfmx_fusion_read", "sfmx_fusion_extract",
     "sfmx_fusion_last_us",
+    "sfmx_fusion_extract_normals", "sfmx_fusion_normals_us",
+    "sfmx_shade_default_params", "sfmx_shade_check_params", "sfmx_shade_create", "sfmx_shade_destroy", "sfmx_shade_reset",
+    "sfmx_shade_add_view", "sfmx_shade_add_stereo_view", "sfmx_shade_view_count", "sfmx_shade_vertices", "sfmx_shade_fusion",
+    "sfmx_shade_last_us",
 ]
 
 
@@ -113,6 +117,34 @@ def fusion_view(cam: dict, w: int, h: int) -> FusionView:
     return v
 
 
+class ShadeParams(ctypes.Structure):
+    _fields_ = [("depth_tol", c_double), ("disp_min", c_double), ("cull", c_int), ("fill", c_int)]
+
+
+# depth_tol has no default at this level (pipeline.fuse uses the volume's trunc)
+SHADE_DEFAULTS = dict(disp_min=1.0, cull=1, fill=0)
+
+
+def shade_params(depth_tol=0.0, **kw) -> ShadeParams:
+    unknown = set(kw) - set(SHADE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown shade parameters {sorted(unknown)}")
+    kw = {**SHADE_DEFAULTS, **kw}
+    return ShadeParams(float(depth_tol), float(kw["disp_min"]), int(kw["cull"]), int(kw["fill"]))
+
+
+def shade_default_params() -> dict:
+    """sfmx_shade_default_params as a dict (needs no device)"""
+    p = ShadeParams()
+    load_library().sfmx_shade_default_params(byref(p))
+    return dict(depth_tol=p.depth_tol, disp_min=p.disp_min, cull=p.cull, fill=p.fill)
+
+
+def shade_check_params(**kw) -> bool:
+    """True if sfmx_shade_vertices / _fusion would accept the parameters; needs no device"""
+    return load_library().sfmx_shade_check_params(byref(shade_params(**kw))) == SFMX_OK
+
+
 def stereo_check_params(w: int, h: int, **kw) -> bool:
     """True if sfmx_stereo_create would accept (w, h, params); needs no device"""
     return load_library().sfmx_stereo_check_params(c_int(w), c_int(h), byref(stereo_params(**kw))) == SFMX_OK
@@ -141,6 +173,8 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_debug_klt_slow_steps.restype = c_uint64
         _lib.sfmx_stereo_last_us.restype = c_double
         _lib.sfmx_fusion_last_us.restype = c_double
+        _lib.sfmx_fusion_normals_us.restype = c_double
+        _lib.sfmx_shade_last_us.restype = c_double
     return _lib
 
 
@@ -248,12 +282,99 @@ class Fusion:
         self.ctx._chk(rc)
         return verts[:nv].copy(), faces[:nf].copy()
 
+    def extract_normals(self):
+        """extract() plus normals float64 [n][3]; the vertices and normals stay on the device for Shade.shade_fusion"""
+        nv, nf = self.counts()
+        verts, faces, normals = np.zeros((max(nv, 1), 3)), np.zeros((max(nf, 1), 3), np.int32), np.zeros((max(nv, 1), 3))
+        n1, n2 = c_int(0), c_int(0)
+        self.ctx._chk(self.ctx.lib.sfmx_fusion_extract_normals(self.ctx.h_, self.h_, _p(verts, c_double), c_int(nv), _p(faces, c_int32),
+                                                               c_int(nf), _p(normals, c_double), byref(n1), byref(n2)))
+        return verts[:n1.value].copy(), faces[:n2.value].copy(), normals[:n1.value].copy()
+
     def last_us(self) -> float:
         return float(self.ctx.lib.sfmx_fusion_last_us(self.h_))
+
+    def normals_us(self) -> float:
+        return float(self.ctx.lib.sfmx_fusion_normals_us(self.h_))
 
     def close(self):
         if self.h_:
             self.ctx.lib.sfmx_fusion_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Shade:
+    """sfmx_shade: retained views (camera, disp16 map, left rectified image) on the device, and vertex shading from them."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_shade_create(ctx.h_, byref(self.h_)))
+
+    def add_view(self, cam: dict, disp16, image, shape=None):
+        """disp16 int16 [h][w] and image u8 [h][w]: numpy arrays, or ints (device pointers) with shape=(h, w)"""
+        if isinstance(disp16, int) != isinstance(image, int):
+            raise TypeError("disp16 and image: both host arrays or both device pointers")
+        if isinstance(disp16, int):
+            h, w = shape
+            pd, pi, on_dev = c_void_p(disp16), c_void_p(image), 1
+        else:
+            disp16 = np.ascontiguousarray(disp16, np.int16)
+            image = np.ascontiguousarray(image, np.uint8)
+            h, w = disp16.shape
+            assert image.shape == (h, w)
+            pd, pi, on_dev = disp16.ctypes.data_as(c_void_p), image.ctypes.data_as(c_void_p), 0
+        v = fusion_view(cam, w, h)
+        self.ctx._chk(self.ctx.lib.sfmx_shade_add_view(self.ctx.h_, self.h_, byref(v), pd, pi, c_int(on_dev)))
+
+    def add_stereo_view(self, cam: dict, st: "Stereo"):
+        """the last disparity map and left rectified image st computed, copied on the device"""
+        v = fusion_view(cam, st.w, st.h)
+        self.ctx._chk(self.ctx.lib.sfmx_shade_add_stereo_view(self.ctx.h_, self.h_, byref(v), st.h_))
+
+    def view_count(self) -> int:
+        return int(self.ctx.lib.sfmx_shade_view_count(self.h_))
+
+    def reset(self):
+        self.ctx._chk(self.ctx.lib.sfmx_shade_reset(self.ctx.h_, self.h_))
+
+    def shade(self, verts, normals, depth_tol, n=None, **params):
+        """(grey u8 [n], views int32 [n]).  verts / normals: float64 [n][3] arrays (normals may be None with cull=0), or ints
+        (device pointers) with n given."""
+        p = shade_params(depth_tol, **params)
+        on_dev = isinstance(verts, int)
+        if on_dev:
+            pv, pn = c_void_p(verts), (c_void_p(normals) if normals is not None else None)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            n = len(verts)
+            normals = None if normals is None else _f64(normals).reshape(-1, 3)
+            assert normals is None or len(normals) == n
+            pv, pn = verts.ctypes.data_as(c_void_p), (normals.ctypes.data_as(c_void_p) if normals is not None else None)
+        grey, views = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_shade_vertices(self.ctx.h_, self.h_, pv, pn, c_int(n), c_int(1 if on_dev else 0), byref(p),
+                                                       _p(grey, c_uint8), _p(views, c_int32)))
+        return grey[:n].copy(), views[:n].copy()
+
+    def shade_fusion(self, fu: Fusion, n: int, depth_tol, **params):
+        """the n vertices fu.extract_normals() left on the device: (grey u8 [n], views int32 [n])"""
+        p = shade_params(depth_tol, **params)
+        grey, views = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_shade_fusion(self.ctx.h_, self.h_, fu.h_, byref(p), _p(grey, c_uint8), _p(views, c_int32)))
+        return grey[:n].copy(), views[:n].copy()
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_shade_last_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_shade_destroy(self.ctx.h_, self.h_)
             self.h_ = c_void_p()
 
     def __del__(self):
@@ -579,6 +700,9 @@ class Context:
 
     def fusion(self, origin, voxel, dims, **params) -> "Fusion":
         return Fusion(self, origin, voxel, dims, **params)
+
+    def shade(self) -> "Shade":
+        return Shade(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

@@ -15,6 +15,8 @@
 //                      inter-workgroup hand-off inside a launch)
 //   k_fu_emit_verts    one thread per grid point: its used slots, in slot order
 //   k_fu_emit_faces    one thread per cell: its triangles, in (tet, triangle) order
+//   k_fu_emit_normals  one thread per grid point, as k_fu_emit_verts: the volume's gradient at both ends of each used edge,
+//                      interpolated with the vertex's own t and normalised
 #include <cmath>
 
 #include "sfmx_internal.h"
@@ -284,6 +286,59 @@ __global__ __launch_bounds__(256) void k_fu_emit_verts(const double* __restrict_
   }
 }
 
+// ---- vertex normals: the gradient of s ------------------------------------------------------------------------
+// one axis of the gradient at a defined grid point with value s: central where both neighbours are defined, one-sided where
+// one is, 0 where neither (a neighbour outside the grid is undefined)
+__device__ __forceinline__ double fu_grad_axis(const double* __restrict__ sum, const int* __restrict__ cnt, int minw, double s, size_t L,
+                                               size_t stride, bool in_p, bool in_m) {
+  double sp = 0.0, sm = 0.0;
+  const bool dp = in_p && fu_value(sum, cnt, L + stride, minw, sp);
+  const bool dm = in_m && fu_value(sum, cnt, L - stride, minw, sm);
+  return dp && dm ? (sp - sm) * 0.5 : dp ? sp - s : dm ? s - sm : 0.0;
+}
+
+__device__ __forceinline__ void fu_grad(const double* __restrict__ sum, const int* __restrict__ cnt, const FuGrid& g, int i, int j, int k,
+                                        size_t L, double s, double& G0, double& G1, double& G2) {
+  const size_t sy = (size_t)g.nx, sz = (size_t)g.nx * g.ny;
+  G0 = fu_grad_axis(sum, cnt, g.minw, s, L, 1, i + 1 < g.nx, i > 0);
+  G1 = fu_grad_axis(sum, cnt, g.minw, s, L, sy, j + 1 < g.ny, j > 0);
+  G2 = fu_grad_axis(sum, cnt, g.minw, s, L, sz, k + 1 < g.nz, k > 0);
+}
+
+__global__ __launch_bounds__(256) void k_fu_emit_normals(const double* __restrict__ sum, const int* __restrict__ cnt, FuGrid g, int n,
+                                                         const unsigned* __restrict__ vmask, const int* __restrict__ voff,
+                                                         double* __restrict__ normals) {
+  const int L = blockIdx.x * 256 + threadIdx.x;
+  if (L >= n) return;
+  const unsigned mask = vmask[L];
+  if (!mask) return;
+  const int i = L % g.nx, j = (L / g.nx) % g.ny, k = L / (g.nx * g.ny);
+  double sg;
+  (void)fu_value(sum, cnt, (size_t)L, g.minw, sg);
+  double Gg0, Gg1, Gg2;
+  fu_grad(sum, cnt, g, i, j, k, (size_t)L, sg, Gg0, Gg1, Gg2);
+  constexpr int D[7][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {1, 1, 0}, {1, 0, 1}, {0, 1, 1}, {1, 1, 1}};
+  size_t o = (size_t)voff[L];
+#pragma unroll
+  for (int sl = 0; sl < 7; sl++) {
+    if (!((mask >> sl) & 1u)) continue;
+    const int di = D[sl][0], dj = D[sl][1], dk = D[sl][2];
+    const size_t Lq = (size_t)L + di + (size_t)dj * g.nx + (size_t)dk * ((size_t)g.nx * g.ny);
+    double sq;
+    (void)fu_value(sum, cnt, Lq, g.minw, sq);
+    const double t = sg / (sg - sq);
+    double Gq0, Gq1, Gq2;
+    fu_grad(sum, cnt, g, i + di, j + dj, k + dk, Lq, sq, Gq0, Gq1, Gq2);
+    const double N0 = Gg0 + t * (Gq0 - Gg0), N1 = Gg1 + t * (Gq1 - Gg1), N2 = Gg2 + t * (Gq2 - Gg2);
+    const double len = sqrt((N0 * N0 + N1 * N1) + N2 * N2);
+    const bool ok = len > 0.0;
+    normals[3 * o + 0] = ok ? N0 / len : 0.0;
+    normals[3 * o + 1] = ok ? N1 / len : 0.0;
+    normals[3 * o + 2] = ok ? N2 / len : 0.0;
+    o++;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_fu_emit_faces(const double* __restrict__ sum, const int* __restrict__ cnt, FuGrid g, int n,
                                                        const int* __restrict__ tri_cnt, const int* __restrict__ foff,
                                                        const unsigned* __restrict__ vmask, const int* __restrict__ voff,
@@ -322,8 +377,11 @@ struct sfmx_fusion {
   long long stack_used = 0;
   // extraction: triangle counts, face offsets, slot masks, vertex offsets (int32 [n] each), scan partials, totals
   DevBuf ex, out_v, out_f;
-  hipEvent_t ev[4] = {};
-  double last_us = 0.0;
+  // the last sfmx_fusion_extract_normals: normals next to out_v, and how many vertices of both are current (-1: none)
+  DevBuf out_n;
+  int resident = -1;
+  hipEvent_t ev[6] = {};
+  double last_us = 0.0, normals_us = 0.0;
 };
 
 namespace {
@@ -441,7 +499,7 @@ int sfmx_fusion_create(sfmx_ctx* ctx, const sfmx_fusion_params* p, sfmx_fusion**
   hipError_t e = hipMalloc(&fu->sum, n * 8);
   if (e == hipSuccess) e = hipMalloc(&fu->cnt, n * 4);
   if (e == hipSuccess) e = hipMalloc(&fu->d_views, sizeof(FuView) * (size_t)p->max_views);
-  for (int q = 0; q < 4 && e == hipSuccess; q++) e = hipEventCreate(&fu->ev[q]);
+  for (int q = 0; q < 6 && e == hipSuccess; q++) e = hipEventCreate(&fu->ev[q]);
   if (e == hipSuccess) e = hipMemsetAsync(fu->sum, 0, n * 8, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(fu->cnt, 0, n * 4, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -467,6 +525,7 @@ void sfmx_fusion_destroy(sfmx_ctx* ctx, sfmx_fusion* fu) {
   fu->ex.release();
   fu->out_v.release();
   fu->out_f.release();
+  fu->out_n.release();
   for (hipEvent_t ev : fu->ev)
     if (ev) (void)hipEventDestroy(ev);
   delete fu;
@@ -483,6 +542,8 @@ int sfmx_fusion_reset(sfmx_ctx* ctx, sfmx_fusion* fu) {
   fu->pending.clear();
   fu->stack_used = 0;
   fu->last_us = 0.0;
+  fu->normals_us = 0.0;
+  fu->resident = -1;
   return SFMX_OK;
 }
 
@@ -508,6 +569,7 @@ int sfmx_fusion_integrate(sfmx_ctx* ctx, sfmx_fusion* fu) {
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int nv = (int)fu->pending.size();
+  fu->resident = -1;  // the volume changes: the surface kept on the device is no longer its surface
   SFMX_HIP(ctx, hipMemcpyAsync(fu->d_views, fu->pending.data(), sizeof(FuView) * (size_t)nv, hipMemcpyHostToDevice, s));
   const FuGrid g = fu_grid(fu);
   const int bx = (g.nx + 63) / 64, by = (g.ny + 3) / 4;
@@ -533,8 +595,9 @@ int sfmx_fusion_read(sfmx_ctx* ctx, sfmx_fusion* fu, double* sum, int32_t* count
   return SFMX_OK;
 }
 
-int sfmx_fusion_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts_cap, int32_t* faces, int faces_cap, int* n_verts,
-                        int* n_faces) {
+// sfmx_fusion_extract, and with want_normals sfmx_fusion_extract_normals: the same launches, then the normals
+static int fu_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts_cap, int32_t* faces, int faces_cap, bool want_normals,
+               double* normals, int* n_verts, int* n_faces) {
   SFMX_REQUIRE(ctx, ctx && fu && n_verts && n_faces);
   *n_verts = 0;
   *n_faces = 0;
@@ -569,8 +632,10 @@ int sfmx_fusion_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts
   const int nf = tot[0], nvx = tot[1];
   *n_faces = nf;
   *n_verts = nvx;
-  if (!verts && !faces) return SFMX_OK;
-  SFMX_REQUIRE(ctx, verts && faces && verts_cap >= nvx && faces_cap >= nf);
+  if (!verts && !faces && !normals) return SFMX_OK;
+  SFMX_REQUIRE(ctx, verts && faces && verts_cap >= nvx && faces_cap >= nf && (!want_normals || normals));
+  fu->resident = want_normals ? 0 : -1;  // out_v is rewritten below
+  fu->normals_us = 0.0;
   if (nf == 0) return SFMX_OK;
   SFMX_HIP(ctx, fu->out_v.ensure((size_t)nvx * 24));
   SFMX_HIP(ctx, fu->out_f.ensure((size_t)nf * 12));
@@ -581,8 +646,40 @@ int sfmx_fusion_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts
   if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(fu->ev[3], s));
   SFMX_HIP(ctx, hipMemcpyAsync(verts, fu->out_v.p, (size_t)nvx * 24, hipMemcpyDeviceToHost, s));
   SFMX_HIP(ctx, hipMemcpyAsync(faces, fu->out_f.p, (size_t)nf * 12, hipMemcpyDeviceToHost, s));
+  if (want_normals) {
+    SFMX_HIP(ctx, fu->out_n.ensure((size_t)nvx * 24));
+    if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(fu->ev[4], s));
+    k_fu_emit_normals<<<nb, 256, 0, s>>>(fu->sum, fu->cnt, g, n, vmask, voff, fu->out_n.as<double>());
+    SFMX_HIP(ctx, hipGetLastError());
+    if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(fu->ev[5], s));
+    SFMX_HIP(ctx, hipMemcpyAsync(normals, fu->out_n.p, (size_t)nvx * 24, hipMemcpyDeviceToHost, s));
+  }
   SFMX_HIP(ctx, hipStreamSynchronize(s));
+  if (want_normals) {
+    fu->resident = nvx;
+    float ms = 0.f;
+    if (ctx->timing && hipEventElapsedTime(&ms, fu->ev[4], fu->ev[5]) == hipSuccess) fu->normals_us = (double)ms * 1000.0;
+    fu->last_us += fu->normals_us;
+  }
   return fu_timed(ctx, fu, 2, 3);
 }
 
+int sfmx_fusion_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts_cap, int32_t* faces, int faces_cap, int* n_verts,
+                        int* n_faces) {
+  return fu_extract(ctx, fu, verts, verts_cap, faces, faces_cap, false, nullptr, n_verts, n_faces);
+}
+
+int sfmx_fusion_extract_normals(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts_cap, int32_t* faces, int faces_cap,
+                                double* normals, int* n_verts, int* n_faces) {
+  return fu_extract(ctx, fu, verts, verts_cap, faces, faces_cap, true, normals, n_verts, n_faces);
+}
+
+double sfmx_fusion_normals_us(const sfmx_fusion* fu) { return fu ? fu->normals_us : 0.0; }
+
 }  // extern "C"
+
+int sfmx_fusion_device_surface(const sfmx_fusion* fu, const double** verts, const double** normals) {
+  *verts = fu->out_v.as<double>();
+  *normals = fu->out_n.as<double>();
+  return fu->resident;
+}

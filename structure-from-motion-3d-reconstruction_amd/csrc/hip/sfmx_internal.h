@@ -144,6 +144,10 @@ int sfmx_fail(sfmx_ctx* ctx, int status, const char* what, hipError_t e);
 int sfmx_pyramid_settle(sfmx_ctx* ctx, const sfmx_pyramid* pyr);  // image.hip: order the main stream behind an asynchronous build
 extern "C" void sfmx_release_graphs(sfmx_ctx* ctx);  // image.hip: drop the hipGraph executables cached for this context
 const int16_t* sfmx_stereo_device_disp16(const sfmx_stereo* st, int* w, int* h);  // stereo.hip: the last disparity map on the device
+const uint8_t* sfmx_stereo_device_rect_left(const sfmx_stereo* st, int* w, int* h);  // stereo.hip: the last left rectified image, u8 [h][w]
+// fusion.hip: vertices and normals (double [n][3] each) of the last sfmx_fusion_extract_normals on the device; returns n, or -1
+// when there is none (never extracted, or the volume or the vertex buffer has changed since)
+int sfmx_fusion_device_surface(const sfmx_fusion* fu, const double** verts, const double** normals);
 
 #define SFMX_HIP(ctx, call)                                                         \
   do {                                                                              \

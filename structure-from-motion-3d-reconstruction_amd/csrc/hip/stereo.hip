@@ -301,6 +301,12 @@ const int16_t* sfmx_stereo_device_disp16(const sfmx_stereo* st, int* w, int* h) 
   return st->d16;
 }
 
+const uint8_t* sfmx_stereo_device_rect_left(const sfmx_stereo* st, int* w, int* h) {
+  *w = st->w;
+  *h = st->h;
+  return st->rect;  // plane 0 of u8 [2][h][w]
+}
+
 extern "C" {
 
 void sfmx_stereo_default_params(sfmx_stereo_params* p) {

@@ -6,6 +6,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -24,6 +26,12 @@
 #pragma weak sfmx_fusion_add_stereo_view
 #pragma weak sfmx_fusion_integrate
 #pragma weak sfmx_fusion_extract
+#pragma weak sfmx_fusion_extract_normals
+#pragma weak sfmx_shade_check_params
+#pragma weak sfmx_shade_create
+#pragma weak sfmx_shade_destroy
+#pragma weak sfmx_shade_add_stereo_view
+#pragma weak sfmx_shade_fusion
 
 namespace {
 
@@ -31,15 +39,54 @@ struct Guard {
   sfmx_ctx* ctx;
   sfmx_stereo* st = nullptr;
   sfmx_fusion* fu = nullptr;
+  sfmx_shade* sh = nullptr;
   ~Guard() {
     if (st) sfmx_stereo_destroy(ctx, st);
     if (fu) sfmx_fusion_destroy(ctx, fu);
+    if (sh) sfmx_shade_destroy(ctx, sh);
   }
 };
+
+// write_mesh_ply's file with nx ny nz (float) and red green blue (uchar, the grey three times) after x y z, which are printed
+// exactly as write_mesh_ply prints them; the normals with 9 significant digits, enough to give back the same float
+void write_mesh_ply_appearance(const std::string& path, const sfmx_fusion_result_ex& r) {
+  std::ofstream f(path);
+  if (!f) throw std::runtime_error("Failed to write: " + path);
+  f << "ply\nformat ascii 1.0\n"
+    << "element vertex " << r.n_verts << "\n"
+    << "property float x\nproperty float y\nproperty float z\n"
+    << "property float nx\nproperty float ny\nproperty float nz\n"
+    << "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    << "element face " << r.n_faces << "\n"
+    << "property list uchar int vertex_indices\n"
+    << "end_header\n";
+  const auto prec = f.precision();
+  for (int i = 0; i < r.n_verts; i++) {
+    const double* p = r.verts + 3 * (size_t)i;
+    const double* n = r.normals + 3 * (size_t)i;
+    const int g = r.grey[i];
+    f << p[0] << " " << p[1] << " " << p[2] << " ";
+    f.precision(9);
+    f << (float)n[0] << " " << (float)n[1] << " " << (float)n[2];
+    f.precision(prec);
+    f << " " << g << " " << g << " " << g << "\n";
+  }
+  for (int i = 0; i < r.n_faces; i++) f << "3 " << r.faces[3 * i] << " " << r.faces[3 * i + 1] << " " << r.faces[3 * i + 2] << "\n";
+}
 
 }  // namespace
 
 extern "C" {
+
+void sfmx_host_fusion_free_ex(sfmx_fusion_result_ex* res) {
+  if (!res) return;
+  std::free(res->verts);
+  std::free(res->faces);
+  std::free(res->normals);
+  std::free(res->grey);
+  std::free(res->views);
+  *res = sfmx_fusion_result_ex{};
+}
 
 void sfmx_host_fusion_free(sfmx_fusion_result* res) {
   if (!res) return;
@@ -53,19 +100,42 @@ void sfmx_host_fusion_free(sfmx_fusion_result* res) {
 int sfmx_host_fusion_mesh(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
                           const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp, const sfmx_fusion_params* fp,
                           sfmx_fusion_result* res, const char* ply_path, char* warn, int warn_cap) {
+  if (!res) return SFMX_ERR_INVALID;
+  sfmx_fusion_result_ex ex{};
+  const int rc = sfmx_host_fusion_mesh_ex(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, nullptr, &ex, ply_path, warn, warn_cap);
+  *res = sfmx_fusion_result{ex.verts, ex.faces, ex.n_verts, ex.n_faces, ex.n_views};
+  return rc;
+}
+
+int sfmx_host_fusion_mesh_ex(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, sfmx_fusion_result_ex* res, const char* ply_path,
+                             char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
-  *res = sfmx_fusion_result{};
+  *res = sfmx_fusion_result_ex{};
   if (warn && warn_cap > 0) warn[0] = 0;
   if (!&sfmx_fusion_create || !&sfmx_stereo_disparity) return SFMX_ERR_UNSUPPORTED;
+  if (app && (!&sfmx_shade_create || !&sfmx_fusion_extract_normals)) return SFMX_ERR_UNSUPPORTED;
   int rc = sfmx_stereo_check_params(w, h, sp);
   if (rc != SFMX_OK) return rc;
   rc = sfmx_fusion_check_params(fp);
   if (rc != SFMX_OK) return rc;
+  sfmx_shade_params ap{};
+  if (app) {
+    ap = *app;
+    if (ap.depth_tol == 0.0) ap.depth_tol = fp->trunc == 0.0 ? 4.0 * fp->voxel : fp->trunc;  // the volume's resolved trunc
+    rc = sfmx_shade_check_params(&ap);
+    if (rc != SFMX_OK) return rc;
+  }
   std::string log;
   Guard g{ctx};
   rc = sfmx_fusion_create(ctx, fp, &g.fu);
   if (rc != SFMX_OK) return rc;
+  if (app) {
+    rc = sfmx_shade_create(ctx, &g.sh);
+    if (rc != SFMX_OK) return rc;
+  }
   std::vector<int16_t> d16((size_t)w * h);  // sfmx_stereo_disparity always returns the map to the host
   for (int q = 0; q < m; q++) {
     const int a = pairs[2 * q], b = pairs[2 * q + 1];
@@ -103,6 +173,10 @@ int sfmx_host_fusion_mesh(sfmx_ctx* ctx, const uint8_t* const* images, int on_de
     v.h = h;
     rc = sfmx_fusion_add_stereo_view(ctx, g.fu, &v, g.st);
     if (rc != SFMX_OK) return rc;
+    if (app) {
+      rc = sfmx_shade_add_stereo_view(ctx, g.sh, &v, g.st);
+      if (rc != SFMX_OK) return rc;
+    }
     res->n_views++;
   }
   rc = sfmx_fusion_integrate(ctx, g.fu);
@@ -113,13 +187,27 @@ int sfmx_host_fusion_mesh(sfmx_ctx* ctx, const uint8_t* const* images, int on_de
   if (nf > 0) {
     res->verts = static_cast<double*>(std::malloc((size_t)nv * 3 * sizeof(double)));
     res->faces = static_cast<int32_t*>(std::malloc((size_t)nf * 3 * sizeof(int32_t)));
-    if (!res->verts || !res->faces) {
-      sfmx_host_fusion_free(res);
+    if (app) {
+      res->normals = static_cast<double*>(std::malloc((size_t)nv * 3 * sizeof(double)));
+      res->grey = static_cast<uint8_t*>(std::malloc((size_t)nv));
+      res->views = static_cast<int32_t*>(std::malloc((size_t)nv * sizeof(int32_t)));
+    }
+    if (!res->verts || !res->faces || (app && (!res->normals || !res->grey || !res->views))) {
+      const int keep = res->n_views;
+      sfmx_host_fusion_free_ex(res);
+      res->n_views = keep;
       return SFMX_ERR_INVALID;
     }
-    rc = sfmx_fusion_extract(ctx, g.fu, res->verts, nv, res->faces, nf, &nv, &nf);
+    if (app) {
+      rc = sfmx_fusion_extract_normals(ctx, g.fu, res->verts, nv, res->faces, nf, res->normals, &nv, &nf);
+      if (rc == SFMX_OK) rc = sfmx_shade_fusion(ctx, g.sh, g.fu, &ap, res->grey, res->views);
+    } else {
+      rc = sfmx_fusion_extract(ctx, g.fu, res->verts, nv, res->faces, nf, &nv, &nf);
+    }
     if (rc != SFMX_OK) {
-      sfmx_host_fusion_free(res);
+      const int keep = res->n_views;
+      sfmx_host_fusion_free_ex(res);
+      res->n_views = keep;
       return rc;
     }
     res->n_verts = nv;
@@ -128,6 +216,12 @@ int sfmx_host_fusion_mesh(sfmx_ctx* ctx, const uint8_t* const* images, int on_de
   if (ply_path) {
     if (nf == 0) {
       log += "WARN: fused mesh export skipped (no faces)\n";
+    } else if (app) {
+      try {
+        write_mesh_ply_appearance(ply_path, *res);
+      } catch (const std::exception& e) {
+        log += std::string("WARN: fused mesh export failed (") + e.what() + ")\n";
+      }
     } else {
       std::vector<sfmx_host::V3> vv((size_t)nv);
       for (int i = 0; i < nv; i++) vv[(size_t)i] = sfmx_host::V3{res->verts[3 * i], res->verts[3 * i + 1], res->verts[3 * i + 2]};

@@ -23,4 +23,23 @@ int sfmx_host_fusion_mesh(sfmx_ctx* ctx, const uint8_t* const* images, int on_de
                           const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp, const sfmx_fusion_params* fp,
                           sfmx_fusion_result* res, const char* ply_path, char* warn, int warn_cap);
 void sfmx_host_fusion_free(sfmx_fusion_result* res);
+
+// sfmx_host_fusion_mesh with appearance.  app = NULL: exactly sfmx_host_fusion_mesh (normals / grey / views stay
+// NULL, the PLY is the same file).  Otherwise every integrated pair is also kept as a shade view, the surface is extracted with
+// normals and shaded on the device: normals double [n_verts][3], grey u8 [n_verts], views int32 [n_verts] (views that saw the
+// vertex).  app->depth_tol = 0 means the volume's resolved trunc.  The PLY then carries nx ny nz (float) and red green blue
+// (uchar, the grey three times) per vertex.  Release with sfmx_host_fusion_free_ex.
+struct sfmx_fusion_result_ex {
+  double* verts;
+  int32_t* faces;
+  int n_verts, n_faces, n_views;
+  double* normals;
+  uint8_t* grey;
+  int32_t* views;
+};
+int sfmx_host_fusion_mesh_ex(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, sfmx_fusion_result_ex* res, const char* ply_path,
+                             char* warn, int warn_cap);
+void sfmx_host_fusion_free_ex(sfmx_fusion_result_ex* res);
 }

@@ -175,6 +175,14 @@ class FusionResult(ctypes.Structure):
     _fields_ = [("verts", POINTER(c_double)), ("faces", POINTER(c_int)), ("n_verts", c_int), ("n_faces", c_int), ("n_views", c_int)]
 
 
+class FusionResultEx(ctypes.Structure):
+    _fields_ = [("verts", POINTER(c_double)), ("faces", POINTER(c_int)), ("n_verts", c_int), ("n_faces", c_int), ("n_views", c_int),
+                ("normals", POINTER(c_double)), ("grey", POINTER(c_ubyte)), ("views", POINTER(c_int))]
+
+
+APPEARANCE_KEYS = ("depth_tol", "cull", "fill")
+
+
 def _split_fusion_params(params: dict):
     unknown = set(params) - set(capi.STEREO_DEFAULTS) - set(capi.FUSION_DEFAULTS)
     if unknown:
@@ -183,12 +191,16 @@ def _split_fusion_params(params: dict):
     return sp, {k: v for k, v in params.items() if k in capi.FUSION_DEFAULTS}
 
 
-def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, **params) -> dict:
+def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
+         **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
     explicit: dims = (nx, ny, nz) grid points at origin + (i, j, k) * voxel.  params: capi.STEREO_DEFAULTS and
-    capi.FUSION_DEFAULTS keys.  Returns dict(verts, faces, views (pairs integrated), warn (WARN lines or None))."""
+    capi.FUSION_DEFAULTS keys.  Returns dict(verts, faces, views (pairs integrated), warn (WARN lines or None)).
+    appearance: True, or dict(depth_tol=, cull=, fill=) (depth_tol defaults to the volume's trunc) -- vertex normals from the
+    volume's gradient and vertex grey from the views that see each vertex: the dict gains normals [n][3] f64,
+    grey [n] u8 and vertex_views [n] i32 (views that saw the vertex), and the PLY gains nx ny nz and red green blue."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -207,9 +219,34 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     sp, fkw = _split_fusion_params(params)
     fp = capi.fusion_params(origin, voxel, dims, **fkw)
     K = np.ascontiguousarray(K, np.float64).reshape(9)
-    res = FusionResult()
     warn = ctypes.create_string_buffer(1 << 16)
     dp = POINTER(c_double)
+    if appearance:
+        akw = {} if appearance is True else dict(appearance)
+        unknown = set(akw) - set(APPEARANCE_KEYS)
+        if unknown:
+            raise TypeError(f"unknown appearance parameters {sorted(unknown)}")
+        ap = capi.shade_params(akw.pop("depth_tol", 0.0), disp_min=fp.disp_min, **akw)  # 0 = the volume's trunc
+        rex = FusionResultEx()
+        rc = lib.sfmx_host_fusion_mesh_ex(ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp),
+                                          poses12.ctypes.data_as(dp), pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp),
+                                          byref(fp), byref(ap), byref(rex), ply_path.encode() if ply_path else None, warn,
+                                          c_int(len(warn)))
+        if rc != capi.SFMX_OK:
+            raise capi.SfmxError(rc, (ctx.lib.sfmx_last_error(ctx.h_) or b"").decode() or "fuse")
+        try:
+            nv, nf = (rex.n_verts, rex.n_faces) if rex.n_faces else (0, 0)
+            verts = np.ctypeslib.as_array(rex.verts, (nv, 3)).copy() if nf else np.zeros((0, 3))
+            faces = np.ctypeslib.as_array(rex.faces, (nf, 3)).astype(np.int32) if nf else np.zeros((0, 3), np.int32)
+            normals = np.ctypeslib.as_array(rex.normals, (nv, 3)).copy() if nf else np.zeros((0, 3))
+            grey = np.ctypeslib.as_array(rex.grey, (nv,)).copy() if nf else np.zeros(0, np.uint8)
+            vviews = np.ctypeslib.as_array(rex.views, (nv,)).astype(np.int32) if nf else np.zeros(0, np.int32)
+            n_views = int(rex.n_views)
+        finally:
+            lib.sfmx_host_fusion_free_ex(byref(rex))
+        return dict(verts=verts, faces=faces, views=n_views, warn=warn.value.decode() or None, normals=normals, grey=grey,
+                    vertex_views=vviews)
+    res = FusionResult()
     rc = lib.sfmx_host_fusion_mesh(ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp),
                                    poses12.ctypes.data_as(dp), pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp),
                                    byref(res), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
@@ -252,7 +289,7 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     rect), and out_dir gains templeRing_mesh_stereo_kf{a}_kf{b}.ply (a skipped export writes no file and one WARN log line).
     fusion (optional): {'pairs': [(a, b), ...], 'origin', 'voxel', 'dims', **params} (keyframe indices; params as fuse) -- after
     the run, fuse() on the run's own keyframe frames and kf_poses: the result gains fused_mesh = fuse()'s dict, and out_dir
-    gains templeRing_mesh_fused.ply.  The run itself, its log and every other output are unchanged.
+    gains templeRing_mesh_fused.ply; 'appearance' (True or a dict, as fuse) adds normals and vertex grey to both.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -313,7 +350,9 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         else:
             imgs, fshape = [int(images_dev) + f * h * w for f in frames], (h, w)
         ply = os.path.join(out_dir, "templeRing_mesh_fused.ply") if out_dir else None
-        out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply, **fz)
+        appearance = fz.pop("appearance", False)
+        out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
+                                 appearance=appearance, **fz)
     return out
 
 

@@ -446,6 +446,16 @@ class BaProblem:
         ctx._chk(ctx.lib.sfmx_ba_create(ctx.h_, c_int(W), c_int(self.P), _p(X, c_double), _p(obs_ptr, c_int32),
                                         _p(obs_li, c_int32), _p(obs_uv, c_double), byref(self.h_)))
 
+    def reset(self, W: int, X, obs_ptr, obs_li, obs_uv):
+        """re-target this object at another window (sfmx_ba_reset): the device buffers are kept and only grow"""
+        X = _f64(X)
+        obs_ptr = np.ascontiguousarray(obs_ptr, np.int32)
+        obs_li = np.ascontiguousarray(obs_li, np.int32)
+        obs_uv = _f64(obs_uv)
+        self.ctx._chk(self.ctx.lib.sfmx_ba_reset(self.ctx.h_, self.h_, c_int(W), c_int(X.shape[0]), _p(X, c_double), _p(obs_ptr, c_int32),
+                                                 _p(obs_li, c_int32), _p(obs_uv, c_double)))
+        self.W, self.P = W, X.shape[0]
+
     def build(self, poses_wc, fx, fy, cx, cy, huber, lam, damp=True):
         D = 6 * self.W
         poses = _f64(poses_wc)

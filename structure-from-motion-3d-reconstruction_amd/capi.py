@@ -634,16 +634,17 @@ class Context:
         return ((xy[:m] & 0x7FFF).astype(np.int32), ((xy[:m] >> 16) & 0x7FFF).astype(np.int32), (xy[:m] >> 31).astype(bool),
                 sc[:m].copy(), n.value, ntot.value)
 
-    def klt_track(self, pa: Pyramid, pb: Pyramid, xy, levels=3, radius=5, iters=10, fb=1.0):
+    def klt_track(self, pa: Pyramid, pb: Pyramid, xy, levels=3, radius=5, iters=10, fb=1.0, want_back=True):
+        """want_back=False passes xy_back = NULL (the backward pass still runs: keep needs it); back is then None"""
         xy = _f64(xy).reshape(-1, 2)
         n = xy.shape[0]
         fwd = np.zeros((n, 2))
-        back = np.zeros((n, 2))
+        back = np.zeros((n, 2)) if want_back else None
         keep = np.zeros(n, np.uint8)
         steps = c_uint64()
         cfg = KltCfg(levels, radius, iters, fb)
         self._chk(self.lib.sfmx_klt_track(self.h_, pa.h_, pb.h_, _p(xy, c_double), c_int(n), byref(cfg), _p(fwd, c_double),
-                                          _p(back, c_double), _p(keep, c_uint8), byref(steps)))
+                                          _p(back, c_double) if want_back else None, _p(keep, c_uint8), byref(steps)))
         return fwd, back, keep, steps.value
 
     def klt_slow_steps(self) -> int:

@@ -368,6 +368,50 @@ int sfmx_shade_fusion(sfmx_ctx* ctx, sfmx_shade* sh, const sfmx_fusion* fu, cons
 /* device time (us) of the kernel of the last sfmx_shade_vertices / _fusion when timing is on (sfmx_set_timing), else 0 */
 double sfmx_shade_last_us(const sfmx_shade* sh);
 
+/* ---- multi-view consistency filtering of disparity maps before fusion ----------------------------------- */
+/* A consist object keeps an ordered list of views (a sfmx_fusion_view and its disp16 map, as sfmx_fusion / sfmx_shade take
+ * them).  sfmx_consist_filter keeps a pixel's disparity only if at least min_support OTHER views (other by index), looked up
+ * at the pixel its 3-D point projects to, hold a depth that agrees within rel_tol and whose own 3-D point projects back to
+ * within reproj_px of the pixel; every other pixel becomes -16.  Every test reads the unfiltered maps, the results go to a
+ * second slab, and the support is an integer count of independent tests: IEEE double in one fixed expression order up to
+ * each comparison, so the filtered maps, the support counts and the counters are bit-identical to the NumPy restatement in
+ * tests/consist_ref.py whatever the launch shape. */
+typedef struct sfmx_consist sfmx_consist;  /* retained views: camera and disparity map, and the filtered maps, on the device */
+typedef struct sfmx_consist_params {
+  double rel_tol;    /* the other view's depth Z' agrees when |Z' - q2| <= rel_tol * q2; > 0, finite (default 0.01) */
+  double reproj_px;  /* its point projects back to within this many pixels; >= 0 (default 1.0) */
+  double disp_min;   /* disparities below this (pixels) are invalid, here and in the other views (default 1.0) */
+  int min_support;   /* agreeing other views a pixel needs to be kept; >= 0 (default 2; 0 keeps every valid pixel) */
+} sfmx_consist_params;
+void sfmx_consist_default_params(sfmx_consist_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_consist_check_params(const sfmx_consist_params* p);
+int sfmx_consist_create(sfmx_ctx* ctx, sfmx_consist** out);
+void sfmx_consist_destroy(sfmx_ctx* ctx, sfmx_consist* cs);
+/* drop every view and the result (the device memory is kept for the next ones) */
+int sfmx_consist_reset(sfmx_ctx* ctx, sfmx_consist* cs);
+/* append a view: disp16 int16 [h][w] (x 16, -16 = invalid), a host pointer or (on_device = 1) a device pointer; copied.
+ * Views of different sizes may be mixed; w <= 4096, w * h < 2^30.  There is no view limit: the storage grows. */
+int sfmx_consist_add_view(sfmx_ctx* ctx, sfmx_consist* cs, const sfmx_fusion_view* view, const int16_t* disp16, int on_device);
+/* append the last disparity map sfmx_stereo_disparity computed on st (copied device to device) */
+int sfmx_consist_add_stereo_view(sfmx_ctx* ctx, sfmx_consist* cs, const sfmx_fusion_view* view, const sfmx_stereo* st);
+int sfmx_consist_view_count(const sfmx_consist* cs);
+/* filter every view against every other in one launch; 0 views is not an error.  The result stays valid until a view is
+ * added or the object is reset. */
+int sfmx_consist_filter(sfmx_ctx* ctx, sfmx_consist* cs, const sfmx_consist_params* p);
+/* view i of the last filter to the host: disp16_out int16 [h][w] (the kept disparities, -16 elsewhere) and support_out u8
+ * [h][w] (agreeing views, saturated at 255; 0 where the input is invalid); either may be NULL.  SFMX_ERR_INVALID without a
+ * current result or with i out of range. */
+int sfmx_consist_read(sfmx_ctx* ctx, sfmx_consist* cs, int i, int16_t* disp16_out, uint8_t* support_out);
+/* per view of the last filter: valid_out / kept_out int32 [view count], the pixels that were valid and the pixels kept
+ * (counted on the device); either may be NULL.  SFMX_ERR_INVALID without a current result. */
+int sfmx_consist_counts(sfmx_ctx* ctx, sfmx_consist* cs, int32_t* valid_out, int32_t* kept_out);
+/* queue view i of cs (its camera and its FILTERED map, copied device to device) into fu, as sfmx_fusion_add_view would.
+ * SFMX_ERR_INVALID without a current result or with i out of range. */
+int sfmx_fusion_add_consist_view(sfmx_ctx* ctx, sfmx_fusion* fu, const sfmx_consist* cs, int i);
+/* device time (us) of the kernel of the last sfmx_consist_filter when timing is on (sfmx_set_timing), else 0 */
+double sfmx_consist_last_us(const sfmx_consist* cs);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

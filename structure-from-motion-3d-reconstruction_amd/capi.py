@@ -39,6 +39,9 @@ SYMBOLS = [
     "sfmx_shade_default_params", "sfmx_shade_check_params", "sfmx_shade_create", "sfmx_shade_destroy", "sfmx_shade_reset",
     "sfmx_shade_add_view", "sfmx_shade_add_stereo_view", "sfmx_shade_view_count", "sfmx_shade_vertices", "sfmx_shade_fusion",
     "sfmx_shade_last_us",
+    "sfmx_consist_default_params", "sfmx_consist_check_params", "sfmx_consist_create", "sfmx_consist_destroy", "sfmx_consist_reset",
+    "sfmx_consist_add_view", "sfmx_consist_add_stereo_view", "sfmx_consist_view_count", "sfmx_consist_filter", "sfmx_consist_read",
+    "sfmx_consist_counts", "sfmx_fusion_add_consist_view", "sfmx_consist_last_us",
 ]
 
 
@@ -145,6 +148,33 @@ def shade_check_params(**kw) -> bool:
     return load_library().sfmx_shade_check_params(byref(shade_params(**kw))) == SFMX_OK
 
 
+class ConsistParams(ctypes.Structure):
+    _fields_ = [("rel_tol", c_double), ("reproj_px", c_double), ("disp_min", c_double), ("min_support", c_int)]
+
+
+CONSIST_DEFAULTS = dict(rel_tol=0.01, reproj_px=1.0, disp_min=1.0, min_support=2)
+
+
+def consist_params(**kw) -> ConsistParams:
+    unknown = set(kw) - set(CONSIST_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown consist parameters {sorted(unknown)}")
+    kw = {**CONSIST_DEFAULTS, **kw}
+    return ConsistParams(float(kw["rel_tol"]), float(kw["reproj_px"]), float(kw["disp_min"]), int(kw["min_support"]))
+
+
+def consist_default_params() -> dict:
+    """sfmx_consist_default_params as a dict (needs no device)"""
+    p = ConsistParams()
+    load_library().sfmx_consist_default_params(byref(p))
+    return dict(rel_tol=p.rel_tol, reproj_px=p.reproj_px, disp_min=p.disp_min, min_support=p.min_support)
+
+
+def consist_check_params(**kw) -> bool:
+    """True if sfmx_consist_filter would accept the parameters; needs no device"""
+    return load_library().sfmx_consist_check_params(byref(consist_params(**kw))) == SFMX_OK
+
+
 def stereo_check_params(w: int, h: int, **kw) -> bool:
     """True if sfmx_stereo_create would accept (w, h, params); needs no device"""
     return load_library().sfmx_stereo_check_params(c_int(w), c_int(h), byref(stereo_params(**kw))) == SFMX_OK
@@ -175,6 +205,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_fusion_last_us.restype = c_double
         _lib.sfmx_fusion_normals_us.restype = c_double
         _lib.sfmx_shade_last_us.restype = c_double
+        _lib.sfmx_consist_last_us.restype = c_double
     return _lib
 
 
@@ -247,6 +278,10 @@ class Fusion:
         """the last disparity map st computed, copied on the device"""
         v = fusion_view(cam, st.w, st.h)
         self.ctx._chk(self.ctx.lib.sfmx_fusion_add_stereo_view(self.ctx.h_, self.h_, byref(v), st.h_))
+
+    def add_consist_view(self, cs: "Consist", i: int):
+        """view i of cs with its filtered map (the last cs.filter()), copied on the device"""
+        self.ctx._chk(self.ctx.lib.sfmx_fusion_add_consist_view(self.ctx.h_, self.h_, cs.h_, c_int(i)))
 
     def integrate(self):
         self.ctx._chk(self.ctx.lib.sfmx_fusion_integrate(self.ctx.h_, self.h_))
@@ -375,6 +410,75 @@ class Shade:
     def close(self):
         if self.h_:
             self.ctx.lib.sfmx_shade_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Consist:
+    """sfmx_consist: retained views (camera, disp16 map) on the device, and their multi-view consistency filter."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.shapes = []
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_consist_create(ctx.h_, byref(self.h_)))
+
+    def add_view(self, cam: dict, disp16, shape=None):
+        """disp16: int16 [h][w] numpy array, or an int (device pointer) with shape=(h, w)"""
+        if isinstance(disp16, int):
+            h, w = shape
+            ptr, on_dev = c_void_p(disp16), 1
+        else:
+            disp16 = np.ascontiguousarray(disp16, np.int16)
+            h, w = disp16.shape
+            ptr, on_dev = disp16.ctypes.data_as(c_void_p), 0
+        v = fusion_view(cam, w, h)
+        self.ctx._chk(self.ctx.lib.sfmx_consist_add_view(self.ctx.h_, self.h_, byref(v), ptr, c_int(on_dev)))
+        self.shapes.append((int(h), int(w)))
+
+    def add_stereo_view(self, cam: dict, st: "Stereo"):
+        """the last disparity map st computed, copied on the device"""
+        v = fusion_view(cam, st.w, st.h)
+        self.ctx._chk(self.ctx.lib.sfmx_consist_add_stereo_view(self.ctx.h_, self.h_, byref(v), st.h_))
+        self.shapes.append((int(st.h), int(st.w)))
+
+    def view_count(self) -> int:
+        return int(self.ctx.lib.sfmx_consist_view_count(self.h_))
+
+    def reset(self):
+        self.ctx._chk(self.ctx.lib.sfmx_consist_reset(self.ctx.h_, self.h_))
+        self.shapes = []
+
+    def filter(self, **params):
+        """every view against every other, one launch; params: CONSIST_DEFAULTS keys"""
+        p = consist_params(**params)
+        self.ctx._chk(self.ctx.lib.sfmx_consist_filter(self.ctx.h_, self.h_, byref(p)))
+
+    def read(self, i: int):
+        """(disp16 int16 [h][w], support u8 [h][w]) of view i after the last filter()"""
+        h, w = self.shapes[i] if 0 <= i < len(self.shapes) else (1, 1)
+        d16, sup = np.zeros((h, w), np.int16), np.zeros((h, w), np.uint8)
+        self.ctx._chk(self.ctx.lib.sfmx_consist_read(self.ctx.h_, self.h_, c_int(i), d16.ctypes.data_as(c_void_p), _p(sup, c_uint8)))
+        return d16, sup
+
+    def counts(self):
+        """(valid int32 [n], kept int32 [n]) per view of the last filter()"""
+        n = self.view_count()
+        valid, kept = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_consist_counts(self.ctx.h_, self.h_, _p(valid, c_int32), _p(kept, c_int32)))
+        return valid[:n].copy(), kept[:n].copy()
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_consist_last_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_consist_destroy(self.ctx.h_, self.h_)
             self.h_ = c_void_p()
 
     def __del__(self):
@@ -714,6 +818,9 @@ class Context:
 
     def shade(self) -> "Shade":
         return Shade(self)
+
+    def consist(self) -> "Consist":
+        return Consist(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

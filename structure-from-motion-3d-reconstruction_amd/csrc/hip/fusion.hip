@@ -562,6 +562,15 @@ int sfmx_fusion_add_stereo_view(sfmx_ctx* ctx, sfmx_fusion* fu, const sfmx_fusio
   return fu_queue(ctx, fu, view, d16, hipMemcpyDeviceToDevice);
 }
 
+int sfmx_fusion_add_consist_view(sfmx_ctx* ctx, sfmx_fusion* fu, const sfmx_consist* cs, int i) {
+  SFMX_REQUIRE(ctx, ctx && fu && cs);
+  sfmx_fusion_view v{};
+  const int16_t* d16 = nullptr;
+  SFMX_REQUIRE(ctx, sfmx_consist_device_view(cs, i, &v, &d16));  // no current filter result, or i out of range
+  SFMX_HIP(ctx, hipSetDevice(ctx->device));
+  return fu_queue(ctx, fu, &v, d16, hipMemcpyDeviceToDevice);
+}
+
 int sfmx_fusion_integrate(sfmx_ctx* ctx, sfmx_fusion* fu) {
   SFMX_REQUIRE(ctx, ctx && fu);
   fu->last_us = 0.0;

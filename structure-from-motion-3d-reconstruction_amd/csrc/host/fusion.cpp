@@ -32,6 +32,14 @@
 #pragma weak sfmx_shade_destroy
 #pragma weak sfmx_shade_add_stereo_view
 #pragma weak sfmx_shade_fusion
+#pragma weak sfmx_consist_check_params
+#pragma weak sfmx_consist_create
+#pragma weak sfmx_consist_destroy
+#pragma weak sfmx_consist_add_stereo_view
+#pragma weak sfmx_consist_view_count
+#pragma weak sfmx_consist_filter
+#pragma weak sfmx_consist_counts
+#pragma weak sfmx_fusion_add_consist_view
 
 namespace {
 
@@ -40,7 +48,9 @@ struct Guard {
   sfmx_stereo* st = nullptr;
   sfmx_fusion* fu = nullptr;
   sfmx_shade* sh = nullptr;
+  sfmx_consist* cs = nullptr;
   ~Guard() {
+    if (cs) sfmx_consist_destroy(ctx, cs);
     if (st) sfmx_stereo_destroy(ctx, st);
     if (fu) sfmx_fusion_destroy(ctx, fu);
     if (sh) sfmx_shade_destroy(ctx, sh);
@@ -111,12 +121,21 @@ int sfmx_host_fusion_mesh_ex(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
                              const sfmx_fusion_params* fp, const sfmx_shade_params* app, sfmx_fusion_result_ex* res, const char* ply_path,
                              char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_cs(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, nullptr, nullptr, res, ply_path,
+                                  warn, warn_cap);
+}
+
+int sfmx_host_fusion_mesh_cs(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
   if (warn && warn_cap > 0) warn[0] = 0;
   if (!&sfmx_fusion_create || !&sfmx_stereo_disparity) return SFMX_ERR_UNSUPPORTED;
   if (app && (!&sfmx_shade_create || !&sfmx_fusion_extract_normals)) return SFMX_ERR_UNSUPPORTED;
+  if (cs && (!&sfmx_consist_create || !&sfmx_fusion_add_consist_view)) return SFMX_ERR_UNSUPPORTED;
   int rc = sfmx_stereo_check_params(w, h, sp);
   if (rc != SFMX_OK) return rc;
   rc = sfmx_fusion_check_params(fp);
@@ -128,10 +147,21 @@ int sfmx_host_fusion_mesh_ex(sfmx_ctx* ctx, const uint8_t* const* images, int on
     rc = sfmx_shade_check_params(&ap);
     if (rc != SFMX_OK) return rc;
   }
+  if (cs) {
+    rc = sfmx_consist_check_params(cs);
+    if (rc != SFMX_OK) return rc;
+    if (pair_counts)
+      for (int q = 0; q < 2 * m; q++) pair_counts[q] = -1;
+  }
   std::string log;
   Guard g{ctx};
   rc = sfmx_fusion_create(ctx, fp, &g.fu);
   if (rc != SFMX_OK) return rc;
+  if (cs) {
+    rc = sfmx_consist_create(ctx, &g.cs);
+    if (rc != SFMX_OK) return rc;
+  }
+  std::vector<int> listed;  // with cs: the listed pair behind each consist view
   if (app) {
     rc = sfmx_shade_create(ctx, &g.sh);
     if (rc != SFMX_OK) return rc;
@@ -171,13 +201,33 @@ int sfmx_host_fusion_mesh_ex(sfmx_ctx* ctx, const uint8_t* const* images, int on
     v.B = r.B;
     v.w = w;
     v.h = h;
-    rc = sfmx_fusion_add_stereo_view(ctx, g.fu, &v, g.st);
+    // with cs the view waits in the consist object: its filtered map is queued after the loop
+    rc = cs ? sfmx_consist_add_stereo_view(ctx, g.cs, &v, g.st) : sfmx_fusion_add_stereo_view(ctx, g.fu, &v, g.st);
     if (rc != SFMX_OK) return rc;
+    if (cs) listed.push_back(q);
     if (app) {
       rc = sfmx_shade_add_stereo_view(ctx, g.sh, &v, g.st);
       if (rc != SFMX_OK) return rc;
     }
     res->n_views++;
+  }
+  if (cs) {
+    rc = sfmx_consist_filter(ctx, g.cs, cs);
+    if (rc != SFMX_OK) return rc;
+    const int nc = sfmx_consist_view_count(g.cs);
+    for (int i = 0; i < nc; i++) {
+      rc = sfmx_fusion_add_consist_view(ctx, g.fu, g.cs, i);
+      if (rc != SFMX_OK) return rc;
+    }
+    if (pair_counts && nc > 0) {
+      std::vector<int32_t> valid((size_t)nc), kept((size_t)nc);
+      rc = sfmx_consist_counts(ctx, g.cs, valid.data(), kept.data());
+      if (rc != SFMX_OK) return rc;
+      for (int i = 0; i < nc; i++) {
+        pair_counts[2 * listed[(size_t)i]] = valid[(size_t)i];
+        pair_counts[2 * listed[(size_t)i] + 1] = kept[(size_t)i];
+      }
+    }
   }
   rc = sfmx_fusion_integrate(ctx, g.fu);
   if (rc != SFMX_OK) return rc;

@@ -42,4 +42,14 @@ int sfmx_host_fusion_mesh_ex(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_fusion_params* fp, const sfmx_shade_params* app, sfmx_fusion_result_ex* res, const char* ply_path,
                              char* warn, int warn_cap);
 void sfmx_host_fusion_free_ex(sfmx_fusion_result_ex* res);
+
+// sfmx_host_fusion_mesh_ex with multi-view consistency filtering.  cs = NULL: exactly sfmx_host_fusion_mesh_ex
+// (pair_counts is not touched).  Otherwise each pair's view is kept in a consist object instead of being queued into the
+// volume; after the last pair one sfmx_consist_filter runs over all of them and the filtered maps are queued in the same
+// order.  cs->disp_min is used as given (pipeline.fuse passes the fusion's).  pair_counts (optional) int32 [m][2]: the valid and
+// the kept pixels of each listed pair's view, -1 -1 for a skipped pair.  The shade views of app keep the unfiltered maps.
+int sfmx_host_fusion_mesh_cs(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
 }

@@ -181,6 +181,7 @@ class FusionResultEx(ctypes.Structure):
 
 
 APPEARANCE_KEYS = ("depth_tol", "cull", "fill")
+CONSISTENCY_KEYS = ("rel_tol", "reproj_px", "min_support")
 
 
 def _split_fusion_params(params: dict):
@@ -192,7 +193,7 @@ def _split_fusion_params(params: dict):
 
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
-         **params) -> dict:
+         consistency=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -200,7 +201,11 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     capi.FUSION_DEFAULTS keys.  Returns dict(verts, faces, views (pairs integrated), warn (WARN lines or None)).
     appearance: True, or dict(depth_tol=, cull=, fill=) (depth_tol defaults to the volume's trunc) -- vertex normals from the
     volume's gradient and vertex grey from the views that see each vertex: the dict gains normals [n][3] f64,
-    grey [n] u8 and vertex_views [n] i32 (views that saw the vertex), and the PLY gains nx ny nz and red green blue."""
+    grey [n] u8 and vertex_views [n] i32 (views that saw the vertex), and the PLY gains nx ny nz and red green blue.
+    consistency: True, or dict(rel_tol=, reproj_px=, min_support=) (disp_min is the fusion's) -- every pair's disparity map is
+    filtered against the other pairs' before it enters the volume: the dict gains consistency =
+    dict(valid=[...], kept=[...]), the valid and the kept pixels of each integrated pair.  The shade views of appearance keep
+    the unfiltered maps."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -221,31 +226,46 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     K = np.ascontiguousarray(K, np.float64).reshape(9)
     warn = ctypes.create_string_buffer(1 << 16)
     dp = POINTER(c_double)
+    ap = cp = counts = None
     if appearance:
         akw = {} if appearance is True else dict(appearance)
         unknown = set(akw) - set(APPEARANCE_KEYS)
         if unknown:
             raise TypeError(f"unknown appearance parameters {sorted(unknown)}")
         ap = capi.shade_params(akw.pop("depth_tol", 0.0), disp_min=fp.disp_min, **akw)  # 0 = the volume's trunc
+    if consistency:
+        ckw = {} if consistency is True else dict(consistency)
+        unknown = set(ckw) - set(CONSISTENCY_KEYS)
+        if unknown:
+            raise TypeError(f"unknown consistency parameters {sorted(unknown)}")
+        cp = capi.consist_params(disp_min=fp.disp_min, **ckw)
+        counts = np.full((max(len(pr), 1), 2), -1, np.int32)
+    if ap is not None or cp is not None:
         rex = FusionResultEx()
-        rc = lib.sfmx_host_fusion_mesh_ex(ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp),
-                                          poses12.ctypes.data_as(dp), pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp),
-                                          byref(fp), byref(ap), byref(rex), ply_path.encode() if ply_path else None, warn,
-                                          c_int(len(warn)))
+        head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
+                pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
+        tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
+        if cp is not None:
+            rc = lib.sfmx_host_fusion_mesh_cs(*head, byref(cp), counts.ctypes.data_as(POINTER(c_int)), *tail)
+        else:
+            rc = lib.sfmx_host_fusion_mesh_ex(*head, *tail)
         if rc != capi.SFMX_OK:
             raise capi.SfmxError(rc, (ctx.lib.sfmx_last_error(ctx.h_) or b"").decode() or "fuse")
         try:
             nv, nf = (rex.n_verts, rex.n_faces) if rex.n_faces else (0, 0)
             verts = np.ctypeslib.as_array(rex.verts, (nv, 3)).copy() if nf else np.zeros((0, 3))
             faces = np.ctypeslib.as_array(rex.faces, (nf, 3)).astype(np.int32) if nf else np.zeros((0, 3), np.int32)
-            normals = np.ctypeslib.as_array(rex.normals, (nv, 3)).copy() if nf else np.zeros((0, 3))
-            grey = np.ctypeslib.as_array(rex.grey, (nv,)).copy() if nf else np.zeros(0, np.uint8)
-            vviews = np.ctypeslib.as_array(rex.views, (nv,)).astype(np.int32) if nf else np.zeros(0, np.int32)
-            n_views = int(rex.n_views)
+            out = dict(verts=verts, faces=faces, views=int(rex.n_views), warn=warn.value.decode() or None)
+            if ap is not None:
+                out["normals"] = np.ctypeslib.as_array(rex.normals, (nv, 3)).copy() if nf else np.zeros((0, 3))
+                out["grey"] = np.ctypeslib.as_array(rex.grey, (nv,)).copy() if nf else np.zeros(0, np.uint8)
+                out["vertex_views"] = np.ctypeslib.as_array(rex.views, (nv,)).astype(np.int32) if nf else np.zeros(0, np.int32)
         finally:
             lib.sfmx_host_fusion_free_ex(byref(rex))
-        return dict(verts=verts, faces=faces, views=n_views, warn=warn.value.decode() or None, normals=normals, grey=grey,
-                    vertex_views=vviews)
+        if cp is not None:
+            done = counts[:len(pr)][counts[:len(pr), 0] >= 0]
+            out["consistency"] = dict(valid=[int(v) for v in done[:, 0]], kept=[int(v) for v in done[:, 1]])
+        return out
     res = FusionResult()
     rc = lib.sfmx_host_fusion_mesh(ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp),
                                    poses12.ctypes.data_as(dp), pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp),
@@ -289,7 +309,8 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     rect), and out_dir gains templeRing_mesh_stereo_kf{a}_kf{b}.ply (a skipped export writes no file and one WARN log line).
     fusion (optional): {'pairs': [(a, b), ...], 'origin', 'voxel', 'dims', **params} (keyframe indices; params as fuse) -- after
     the run, fuse() on the run's own keyframe frames and kf_poses: the result gains fused_mesh = fuse()'s dict, and out_dir
-    gains templeRing_mesh_fused.ply; 'appearance' (True or a dict, as fuse) adds normals and vertex grey to both.  The run itself, its log and every other output are unchanged.
+    gains templeRing_mesh_fused.ply; 'appearance' (True or a dict, as fuse) adds normals and vertex grey to both;
+    'consistency' (True or a dict, as fuse) filters the pairs' disparity maps against each other first.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -351,8 +372,9 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
             imgs, fshape = [int(images_dev) + f * h * w for f in frames], (h, w)
         ply = os.path.join(out_dir, "templeRing_mesh_fused.ply") if out_dir else None
         appearance = fz.pop("appearance", False)
+        consistency = fz.pop("consistency", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
-                                 appearance=appearance, **fz)
+                                 appearance=appearance, consistency=consistency, **fz)
     return out
 
 

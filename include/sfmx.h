@@ -412,6 +412,49 @@ int sfmx_fusion_add_consist_view(sfmx_ctx* ctx, sfmx_fusion* fu, const sfmx_cons
 /* device time (us) of the kernel of the last sfmx_consist_filter when timing is on (sfmx_set_timing), else 0 */
 double sfmx_consist_last_us(const sfmx_consist* cs);
 
+/* ---- small connected components of a triangle mesh, removed on the device -------------------------------- */
+/* Two vertices are connected when a face holds both; label(v) is the smallest vertex index of v's component and
+ * comp_faces(v) the number of faces f with label(f[0]) == label(v) (a vertex no face uses is a component of 0 faces).  A
+ * component of cf faces is kept when cf >= 1, cf >= min_faces and cf * 1000 >= largest * min_permille (64-bit; largest = the
+ * greatest cf, so components of equal size are kept or dropped together).  Kept faces stay in input order, kept vertices (those
+ * a kept face uses) in ascending input index with their bytes copied, face indices are renumbered.  Everything is an integer
+ * or a byte copy, so every output is bit-identical to the NumPy restatement in tests/clean_ref.py whatever the schedule. */
+typedef struct sfmx_clean sfmx_clean;  /* device work buffers and the last result; they grow on demand and are kept */
+typedef struct sfmx_clean_params {
+  int min_faces;     /* a kept component has at least this many faces; >= 0 (default 0) */
+  int min_permille;  /* ... and at least this many thousandths of the largest component's faces; 0..1000 (default 10) */
+} sfmx_clean_params;
+void sfmx_clean_default_params(sfmx_clean_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_clean_check_params(const sfmx_clean_params* p);
+int sfmx_clean_create(sfmx_ctx* ctx, sfmx_clean** out);
+void sfmx_clean_destroy(sfmx_ctx* ctx, sfmx_clean* cl);
+/* verts double [n][3] (copied as bytes, never computed with: NaN is allowed), normals double [n][3] or NULL, faces int32
+ * [m][3]; host pointers or (on_device = 1) device pointers, 0 <= n, m < 2^30.  A face index outside [0, n) is found on the
+ * device without any access through it and gives SFMX_ERR_INVALID; the object stays usable.  The four counts (cleaned
+ * vertices and faces, components with at least one face, faces of the largest) may each be NULL. */
+int sfmx_clean_run(sfmx_ctx* ctx, sfmx_clean* cl, const double* verts, const double* normals, int n, const int32_t* faces, int m,
+                   int on_device, const sfmx_clean_params* p, int* n_verts_out, int* n_faces_out, int* n_components, int* largest);
+/* the same for the surface the last sfmx_fusion_extract / _extract_normals with arrays left on the device inside fu (no host
+ * round trip), with its normals when that call made them; SFMX_ERR_INVALID when fu holds none (never extracted, or the volume
+ * has changed since: integrate, reset) */
+int sfmx_clean_fusion(sfmx_ctx* ctx, sfmx_clean* cl, const sfmx_fusion* fu, const sfmx_clean_params* p, int* n_verts_out,
+                      int* n_faces_out, int* n_components, int* largest);
+/* the last successful run to the host: verts_out / normals_out double [n'][3], faces_out int32 [m'][3], vert_src int32 [n'] and
+ * face_src int32 [m'] (the input index of each output element), vert_label / vert_comp_faces int32 [n] (per INPUT vertex); any
+ * may be NULL (normals_out is left alone when the run had no normals).  SFMX_ERR_INVALID before a successful run; a run or
+ * _fusion call that fails for any reason (parameters included) leaves no result. */
+int sfmx_clean_read(sfmx_ctx* ctx, sfmx_clean* cl, double* verts_out, double* normals_out, int32_t* faces_out, int32_t* vert_src,
+                    int32_t* face_src, int32_t* vert_label, int32_t* vert_comp_faces);
+/* the sizes sfmx_clean_read copies by: input vertices and faces (n, m) and cleaned vertices and faces (n', m') of the last
+ * successful run; any pointer may be NULL.  SFMX_ERR_INVALID (and zeros) before a successful run; needs no context. */
+int sfmx_clean_sizes(const sfmx_clean* cl, int* n, int* m, int* n_verts_out, int* n_faces_out);
+/* the cleaned vertices and normals of the last successful run on the device (for sfmx_shade_vertices with on_device = 1);
+ * *normals is NULL when the run had none.  Returns n', or -1 before a successful run.  Valid until the next run on cl. */
+int sfmx_clean_device_surface(const sfmx_clean* cl, const double** verts, const double** normals);
+/* device time (us) of the launches of the last sfmx_clean_run / _fusion when timing is on (sfmx_set_timing), else 0 */
+double sfmx_clean_last_us(const sfmx_clean* cl);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

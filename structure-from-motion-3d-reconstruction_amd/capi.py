@@ -42,6 +42,8 @@ SYMBOLS = [
     "sfmx_consist_default_params", "sfmx_consist_check_params", "sfmx_consist_create", "sfmx_consist_destroy", "sfmx_consist_reset",
     "sfmx_consist_add_view", "sfmx_consist_add_stereo_view", "sfmx_consist_view_count", "sfmx_consist_filter", "sfmx_consist_read",
     "sfmx_consist_counts", "sfmx_fusion_add_consist_view", "sfmx_consist_last_us",
+    "sfmx_clean_default_params", "sfmx_clean_check_params", "sfmx_clean_create", "sfmx_clean_destroy", "sfmx_clean_run",
+    "sfmx_clean_fusion", "sfmx_clean_read", "sfmx_clean_sizes", "sfmx_clean_device_surface", "sfmx_clean_last_us",
 ]
 
 
@@ -175,6 +177,33 @@ def consist_check_params(**kw) -> bool:
     return load_library().sfmx_consist_check_params(byref(consist_params(**kw))) == SFMX_OK
 
 
+class CleanParams(ctypes.Structure):
+    _fields_ = [("min_faces", c_int), ("min_permille", c_int)]
+
+
+CLEAN_DEFAULTS = dict(min_faces=0, min_permille=10)
+
+
+def clean_params(**kw) -> CleanParams:
+    unknown = set(kw) - set(CLEAN_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown clean parameters {sorted(unknown)}")
+    kw = {**CLEAN_DEFAULTS, **kw}
+    return CleanParams(int(kw["min_faces"]), int(kw["min_permille"]))
+
+
+def clean_default_params() -> dict:
+    """sfmx_clean_default_params as a dict (needs no device)"""
+    p = CleanParams()
+    load_library().sfmx_clean_default_params(byref(p))
+    return dict(min_faces=p.min_faces, min_permille=p.min_permille)
+
+
+def clean_check_params(**kw) -> bool:
+    """True if sfmx_clean_run / _fusion would accept the parameters; needs no device"""
+    return load_library().sfmx_clean_check_params(byref(clean_params(**kw))) == SFMX_OK
+
+
 def stereo_check_params(w: int, h: int, **kw) -> bool:
     """True if sfmx_stereo_create would accept (w, h, params); needs no device"""
     return load_library().sfmx_stereo_check_params(c_int(w), c_int(h), byref(stereo_params(**kw))) == SFMX_OK
@@ -206,6 +235,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_fusion_normals_us.restype = c_double
         _lib.sfmx_shade_last_us.restype = c_double
         _lib.sfmx_consist_last_us.restype = c_double
+        _lib.sfmx_clean_last_us.restype = c_double
     return _lib
 
 
@@ -479,6 +509,93 @@ class Consist:
     def close(self):
         if self.h_:
             self.ctx.lib.sfmx_consist_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Clean:
+    """sfmx_clean: small connected components of a triangle mesh removed on the device; the work buffers are kept between calls."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_clean_create(ctx.h_, byref(self.h_)))
+
+    @staticmethod
+    def _counts(out):
+        return dict(n_verts=out[0].value, n_faces=out[1].value, components=out[2].value, largest=out[3].value)
+
+    def run(self, verts, faces, normals=None, n=None, m=None, **params):
+        """verts / normals float64 [n][3] and faces int32 [m][3]: numpy arrays, or ints (device pointers) with n and m given;
+        normals may be None.  params: CLEAN_DEFAULTS keys.  Returns dict(n_verts, n_faces, components, largest)."""
+        p = clean_params(**params)
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int) or (normals is not None and on_dev != isinstance(normals, int)):
+            raise TypeError("verts, normals and faces: all host arrays or all device pointers")
+        if on_dev:
+            pv, pf, pn = c_void_p(verts), c_void_p(faces), (c_void_p(normals) if normals is not None else None)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            n, m = len(verts), len(faces)
+            normals = None if normals is None else _f64(normals).reshape(-1, 3)
+            assert normals is None or len(normals) == n
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+            pn = normals.ctypes.data_as(c_void_p) if normals is not None else None
+        out = [c_int(0) for _ in range(4)]
+        self.ctx._chk(self.ctx.lib.sfmx_clean_run(self.ctx.h_, self.h_, pv, pn, c_int(n), pf, c_int(m), c_int(1 if on_dev else 0),
+                                                  byref(p), *[byref(o) for o in out]))
+        return self._counts(out)
+
+    def fusion(self, fu: "Fusion", **params):
+        """the surface fu.extract() / fu.extract_normals() left on the device; returns run()'s dict"""
+        p = clean_params(**params)
+        out = [c_int(0) for _ in range(4)]
+        self.ctx._chk(self.ctx.lib.sfmx_clean_fusion(self.ctx.h_, self.h_, fu.h_, byref(p), *[byref(o) for o in out]))
+        return self._counts(out)
+
+    def sizes(self):
+        """(n, m, n', m') of the last successful run: input and cleaned vertices and faces; raises before one"""
+        s = [c_int(0) for _ in range(4)]
+        rc = self.ctx.lib.sfmx_clean_sizes(self.h_, *[byref(x) for x in s])
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_clean_sizes: no successful run")
+        return tuple(x.value for x in s)
+
+    def read(self, normals: bool = False):
+        """the last run: dict(verts f64 [n'][3], faces i32 [m'][3], vert_src i32 [n'], face_src i32 [m'], label i32 [n],
+        comp_faces i32 [n]), plus normals f64 [n'][3] when asked for (the run must have had them).  The arrays are sized by what
+        the library says it will copy."""
+        n, _, nv, nf = self.sizes()
+        verts, nrm, faces = np.zeros((max(nv, 1), 3)), np.zeros((max(nv, 1), 3)), np.zeros((max(nf, 1), 3), np.int32)
+        vsrc, fsrc = np.zeros(max(nv, 1), np.int32), np.zeros(max(nf, 1), np.int32)
+        lab, vcf = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_clean_read(self.ctx.h_, self.h_, _p(verts, c_double), _p(nrm, c_double) if normals else None,
+                                                   _p(faces, c_int32), _p(vsrc, c_int32), _p(fsrc, c_int32), _p(lab, c_int32),
+                                                   _p(vcf, c_int32)))
+        out = dict(verts=verts[:nv].copy(), faces=faces[:nf].copy(), vert_src=vsrc[:nv].copy(), face_src=fsrc[:nf].copy(),
+                   label=lab[:n].copy(), comp_faces=vcf[:n].copy())
+        if normals:
+            out["normals"] = nrm[:nv].copy()
+        return out
+
+    def device_surface(self):
+        """(n', device pointer of the cleaned vertices, of the cleaned normals or None); n' = -1 before a successful run"""
+        v, nr = c_void_p(), c_void_p()
+        n = int(self.ctx.lib.sfmx_clean_device_surface(self.h_, byref(v), byref(nr)))
+        return n, v.value, nr.value
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_clean_last_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_clean_destroy(self.ctx.h_, self.h_)
             self.h_ = c_void_p()
 
     def __del__(self):
@@ -821,6 +938,9 @@ class Context:
 
     def consist(self) -> "Consist":
         return Consist(self)
+
+    def clean(self) -> "Clean":
+        return Clean(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

@@ -1,0 +1,447 @@
+// clean.hip — small connected components of an indexed triangle mesh, removed on the device.
+//
+// Exactness: everything is an integer or a byte copy.  Components are a set partition, the smallest index of a set does not
+// depend on the order of the unions, the face counts are integer sums and the output offsets integer scans: any schedule gives
+// the same bytes.  tests/clean_ref.py restates it in NumPy; the tests compare bytes.
+//
+// Kernel layout, one thread per vertex or per face, blocks of 256, all on the context's stream:
+//   k_cl_init        lab[v] = v, cf[v] = 0, vkeep[v] = 0
+//   k_cl_merge       per face: indices outside [0, n) set the flag (atomicOr) and the face is skipped; otherwise unite (v0, v1)
+//                    and (v0, v2).  The union is the speckle filter's (stereo.hip, k_st_uf_*): find both roots, CAS the larger
+//                    root onto the smaller, retry when the CAS fails.  A link only ever points to a smaller index, so there is
+//                    no cycle; a failed CAS means another thread linked that root, so the loop is lock-free, not a wait.
+//                    find halves its path with atomicMin (a label only ever decreases, and only to an ancestor).
+//   k_cl_flatten     lab[v] = find(v)
+//   k_cl_count       per face: cf[lab[v0]] += 1, as one atomicAdd per wave and distinct root (ballot / popcount)
+//   k_cl_stats       per vertex: vcf[v] = cf[lab[v]]; per root with cf > 0 a wave-reduced atomicMax into `largest` and a
+//                    ballot / popcount add into `n_components`
+//   k_cl_mark        per face: the keep rule on cf[lab[v0]]; a kept face flags its three corners
+//   k_cl_scan_*      exclusive int32 scans of the face flags and the vertex flags, one launch per level (fusion.hip's scheme:
+//                    no hand-off between workgroups inside a launch)
+//   k_cl_emit_verts  per kept vertex: its 24 bytes (and its normal's), its input index
+//   k_cl_emit_faces  per kept face: its renumbered indices, its input index
+// No kernel waits on another workgroup or spins on a memory word.  A face with an index out of range is skipped by every
+// per-face kernel (they all run before the host reads the flag), so nothing is ever accessed through such an index.
+#include "sfmx_internal.h"
+
+namespace {
+
+enum { CL_FLAG = 0, CL_LARGEST, CL_NCOMP, CL_NF_OUT, CL_NV_OUT, CL_COUNTERS = 8 };
+
+__device__ __forceinline__ int cl_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// root of x; every second node on the way is re-pointed at its grandparent
+__device__ __forceinline__ int cl_find(int* lab, int x) {
+  while (true) {
+    const int p = cl_load(lab + x);
+    if (p == x) return x;
+    const int g = cl_load(lab + p);
+    if (g == p) return p;
+    atomicMin(&lab[x], g);
+    x = g;
+  }
+}
+
+__device__ __forceinline__ void cl_unite(int* lab, int a, int b) {
+  while (true) {
+    a = cl_find(lab, a);
+    b = cl_find(lab, b);
+    if (a == b) return;
+    const int lo = min(a, b), hi = max(a, b);
+    if (atomicCAS(&lab[hi], hi, lo) == hi) return;  // hi was still a root: linked
+  }
+}
+
+__device__ __forceinline__ bool cl_face(const int* __restrict__ faces, int f, int n, int& v0, int& v1, int& v2) {
+  v0 = faces[3 * (size_t)f];
+  v1 = faces[3 * (size_t)f + 1];
+  v2 = faces[3 * (size_t)f + 2];
+  return (unsigned)v0 < (unsigned)n && (unsigned)v1 < (unsigned)n && (unsigned)v2 < (unsigned)n;
+}
+
+__global__ __launch_bounds__(256) void k_cl_init(int n, int* __restrict__ lab, int* __restrict__ cf, int* __restrict__ vkeep) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= n) return;
+  lab[v] = v;
+  cf[v] = 0;
+  vkeep[v] = 0;
+}
+
+__global__ __launch_bounds__(256) void k_cl_merge(const int* __restrict__ faces, int m, int n, int* lab, int* __restrict__ counters) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= m) return;
+  int v0, v1, v2;
+  if (!cl_face(faces, f, n, v0, v1, v2)) {
+    atomicOr(&counters[CL_FLAG], 1);
+    return;
+  }
+  cl_unite(lab, v0, v1);
+  cl_unite(lab, v0, v2);
+}
+
+__global__ __launch_bounds__(256) void k_cl_flatten(int n, int* lab) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= n) return;
+  const int r = cl_find(lab, v);
+  atomicMin(&lab[v], r);
+}
+
+__global__ __launch_bounds__(256) void k_cl_count(const int* __restrict__ faces, int m, int n, const int* __restrict__ lab,
+                                                  int* __restrict__ cf) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  int v0, v1, v2;
+  const int r = f < m && cl_face(faces, f, n, v0, v1, v2) ? lab[v0] : -1;
+  // one atomicAdd per wave and root: nearly every face of a surface belongs to one component, and a million adds on one
+  // word are served one after the other.  The loop runs on wave-uniform values; nothing is read from memory inside it.
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __ballot(r >= 0);
+  while (todo) {
+    const int leader = __ffsll(todo) - 1;
+    const int rl = __shfl(r, leader, 64);
+    const unsigned long long same = __ballot(r == rl);
+    if (lane == leader) atomicAdd(&cf[rl], __popcll(same));
+    todo &= ~same;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_cl_stats(int n, const int* __restrict__ lab, const int* __restrict__ cf, int* __restrict__ vcf,
+                                                  int* __restrict__ counters) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  int c = 0;  // this thread's component size if it is the root of a component with faces, else 0
+  if (v < n) {
+    const int r = lab[v];
+    const int x = cf[r];
+    vcf[v] = x;
+    if (r == v) c = x;
+  }
+  const unsigned long long roots = __ballot(c > 0);
+  if (roots == 0) return;  // the whole wave
+  int mx = c;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(&counters[CL_LARGEST], mx);
+    atomicAdd(&counters[CL_NCOMP], __popcll(roots));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_cl_mark(const int* __restrict__ faces, int m, int n, const int* __restrict__ lab,
+                                                 const int* __restrict__ cf, const int* __restrict__ counters, int min_faces,
+                                                 int min_permille, int* __restrict__ fkeep, int* vkeep) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= m) return;
+  int v0, v1, v2;
+  bool keep = false;
+  if (cl_face(faces, f, n, v0, v1, v2)) {
+    const int c = cf[lab[v0]];
+    keep = c >= 1 && c >= min_faces && (long long)c * 1000 >= (long long)counters[CL_LARGEST] * min_permille;
+  }
+  fkeep[f] = keep ? 1 : 0;
+  if (keep) {
+    vkeep[v0] = 1;
+    vkeep[v1] = 1;
+    vkeep[v2] = 1;
+  }
+}
+
+// exclusive scan of one 1024-element chunk per block (4 per thread).  in may equal out (every element is read before its
+// block writes).
+__global__ __launch_bounds__(256) void k_cl_scan_local(const int* in, int n, int* out, int* __restrict__ bsum) {
+  __shared__ int wsum[4];
+  const int base = blockIdx.x * 1024 + threadIdx.x * 4;
+  int v[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) v[q] = base + q < n ? in[base + q] : 0;
+  const int tsum = v[0] + v[1] + v[2] + v[3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = tsum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += y;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  int pre = incl - tsum;
+  for (int w = 0; w < wave; w++) pre += wsum[w];
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    if (base + q < n) out[base + q] = pre;
+    pre += v[q];
+  }
+  if (threadIdx.x == 255) bsum[blockIdx.x] = pre;
+}
+
+__global__ __launch_bounds__(256) void k_cl_scan_add(int* out, int n, const int* __restrict__ offs) {
+  const int base = blockIdx.x * 1024 + threadIdx.x * 4;
+  const int o = offs[blockIdx.x];
+#pragma unroll
+  for (int q = 0; q < 4; q++)
+    if (base + q < n) out[base + q] += o;
+}
+
+// counters[slot] = out[n - 1] + in[n - 1]
+__global__ void k_cl_scan_total(const int* __restrict__ in, const int* __restrict__ out, int n, int* __restrict__ counters, int slot) {
+  if (threadIdx.x != 0) return;
+  counters[slot] = out[n - 1] + in[n - 1];
+}
+
+__global__ __launch_bounds__(256) void k_cl_emit_verts(int n, const int* __restrict__ vkeep, const int* __restrict__ voff,
+                                                       const unsigned long long* __restrict__ verts,
+                                                       const unsigned long long* __restrict__ normals,
+                                                       unsigned long long* __restrict__ verts_out,
+                                                       unsigned long long* __restrict__ normals_out, int* __restrict__ vsrc) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= n || !vkeep[v]) return;
+  const size_t o = (size_t)voff[v], i = (size_t)v;
+#pragma unroll
+  for (int a = 0; a < 3; a++) verts_out[3 * o + a] = verts[3 * i + a];
+  if (normals) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) normals_out[3 * o + a] = normals[3 * i + a];
+  }
+  vsrc[o] = v;
+}
+
+__global__ __launch_bounds__(256) void k_cl_emit_faces(const int* __restrict__ faces, int m, const int* __restrict__ fkeep,
+                                                       const int* __restrict__ foff, const int* __restrict__ voff,
+                                                       int* __restrict__ faces_out, int* __restrict__ fsrc) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= m || !fkeep[f]) return;  // a kept face has passed the range check
+  const size_t o = (size_t)foff[f];
+#pragma unroll
+  for (int a = 0; a < 3; a++) faces_out[3 * o + a] = voff[faces[3 * (size_t)f + a]];
+  fsrc[o] = f;
+}
+
+size_t cl_scan_aux(int n) {
+  size_t a = 0;
+  while (n > 1) {
+    n = (n + 1023) / 1024;
+    a += (size_t)n;
+  }
+  return a + 1;
+}
+
+// exclusive scan of in[0..n) into out, n >= 1; aux holds the block sums of every level
+void cl_scan(const int* in, int n, int* out, int* aux, hipStream_t s) {
+  const int nb = (n + 1023) / 1024;
+  k_cl_scan_local<<<nb, 256, 0, s>>>(in, n, out, aux);
+  if (nb > 1) {
+    cl_scan(aux, nb, aux, aux + nb, s);
+    k_cl_scan_add<<<nb, 256, 0, s>>>(out, n, aux);
+  }
+}
+
+}  // namespace
+
+struct sfmx_clean {
+  // per input vertex: lab, cf, vcf, vkeep, voff; per input face: fkeep, foff; then the scans' partials and the counters
+  DevBuf work;
+  DevBuf in_v, in_n, in_f;  // host inputs, staged
+  DevBuf out_v, out_n, out_f, vsrc, fsrc;
+  int *lab = nullptr, *vcf = nullptr;  // into work, of the last successful run
+  bool done = false, has_normals = false;
+  int n = 0, m = 0, nv_out = 0, nf_out = 0;
+  hipEvent_t ev[2] = {};
+  double last_us = 0.0;
+};
+
+namespace {
+
+// verts / normals / faces are device pointers
+int cl_run(sfmx_ctx* ctx, sfmx_clean* cl, const double* verts, const double* normals, int n, const int32_t* faces, int m,
+           const sfmx_clean_params* p, int* n_verts_out, int* n_faces_out, int* n_components, int* largest) {
+  hipStream_t s = ctx->stream;
+  cl->done = false;
+  cl->last_us = 0.0;
+  const size_t nn = (size_t)n, mm = (size_t)m;
+  const size_t aux = cl_scan_aux(n > m ? n : m);
+  SFMX_HIP(ctx, cl->work.ensure((5 * nn + 2 * mm + aux + CL_COUNTERS) * 4));
+  // the outputs are sized by the input: the kept counts are only known on the host after the launches
+  SFMX_HIP(ctx, cl->out_v.ensure(nn * 24));
+  if (normals) SFMX_HIP(ctx, cl->out_n.ensure(nn * 24));
+  SFMX_HIP(ctx, cl->out_f.ensure(mm * 12));
+  SFMX_HIP(ctx, cl->vsrc.ensure(nn * 4));
+  SFMX_HIP(ctx, cl->fsrc.ensure(mm * 4));
+  int* lab = cl->work.as<int>();
+  int* cf = lab + nn;
+  int* vcf = cf + nn;
+  int* vkeep = vcf + nn;
+  int* voff = vkeep + nn;
+  int* fkeep = voff + nn;
+  int* foff = fkeep + mm;
+  int* ax = foff + mm;
+  int* counters = ax + aux;
+  const unsigned nbv = (unsigned)((nn + 255) / 256), nbf = (unsigned)((mm + 255) / 256);
+  if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(cl->ev[0], s));
+  SFMX_HIP(ctx, hipMemsetAsync(counters, 0, CL_COUNTERS * 4, s));
+  if (n > 0) k_cl_init<<<nbv, 256, 0, s>>>(n, lab, cf, vkeep);
+  if (m > 0) k_cl_merge<<<nbf, 256, 0, s>>>(faces, m, n, lab, counters);
+  if (n > 0) k_cl_flatten<<<nbv, 256, 0, s>>>(n, lab);
+  if (m > 0) k_cl_count<<<nbf, 256, 0, s>>>(faces, m, n, lab, cf);
+  if (n > 0) k_cl_stats<<<nbv, 256, 0, s>>>(n, lab, cf, vcf, counters);
+  if (m > 0) {
+    k_cl_mark<<<nbf, 256, 0, s>>>(faces, m, n, lab, cf, counters, p->min_faces, p->min_permille, fkeep, vkeep);
+    cl_scan(fkeep, m, foff, ax, s);
+    k_cl_scan_total<<<1, 64, 0, s>>>(fkeep, foff, m, counters, CL_NF_OUT);
+  }
+  if (n > 0) {
+    cl_scan(vkeep, n, voff, ax, s);
+    k_cl_scan_total<<<1, 64, 0, s>>>(vkeep, voff, n, counters, CL_NV_OUT);
+    k_cl_emit_verts<<<nbv, 256, 0, s>>>(n, vkeep, voff, reinterpret_cast<const unsigned long long*>(verts),
+                                        reinterpret_cast<const unsigned long long*>(normals), cl->out_v.as<unsigned long long>(),
+                                        cl->out_n.as<unsigned long long>(), cl->vsrc.as<int>());
+  }
+  if (m > 0) k_cl_emit_faces<<<nbf, 256, 0, s>>>(faces, m, fkeep, foff, voff, cl->out_f.as<int>(), cl->fsrc.as<int>());
+  SFMX_HIP(ctx, hipGetLastError());
+  if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(cl->ev[1], s));
+  int c[CL_COUNTERS] = {};
+  SFMX_HIP(ctx, hipMemcpyAsync(c, counters, sizeof c, hipMemcpyDeviceToHost, s));
+  SFMX_HIP(ctx, hipStreamSynchronize(s));
+  if (ctx->timing) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, cl->ev[0], cl->ev[1]) == hipSuccess) cl->last_us = (double)ms * 1000.0;
+  }
+  SFMX_REQUIRE(ctx, c[CL_FLAG] == 0);  // a face index outside [0, n)
+  cl->lab = lab;
+  cl->vcf = vcf;
+  cl->n = n;
+  cl->m = m;
+  cl->nv_out = c[CL_NV_OUT];
+  cl->nf_out = c[CL_NF_OUT];
+  cl->has_normals = normals != nullptr;
+  cl->done = true;
+  if (n_verts_out) *n_verts_out = cl->nv_out;
+  if (n_faces_out) *n_faces_out = cl->nf_out;
+  if (n_components) *n_components = c[CL_NCOMP];
+  if (largest) *largest = c[CL_LARGEST];
+  return SFMX_OK;
+}
+
+void cl_zero(int* a, int* b, int* c, int* d) {
+  for (int* q : {a, b, c, d})
+    if (q) *q = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sfmx_clean_default_params(sfmx_clean_params* p) {
+  if (!p) return;
+  *p = sfmx_clean_params{};
+  p->min_faces = 0;
+  p->min_permille = 10;
+}
+
+int sfmx_clean_check_params(const sfmx_clean_params* p) {
+  if (!p) return SFMX_ERR_INVALID;
+  if (p->min_faces < 0 || p->min_permille < 0 || p->min_permille > 1000) return SFMX_ERR_INVALID;
+  return SFMX_OK;
+}
+
+int sfmx_clean_create(sfmx_ctx* ctx, sfmx_clean** out) {
+  SFMX_REQUIRE(ctx, ctx && out);
+  *out = nullptr;
+  SFMX_HIP(ctx, hipSetDevice(ctx->device));
+  auto* cl = new sfmx_clean;
+  hipError_t e = hipEventCreate(&cl->ev[0]);
+  if (e == hipSuccess) e = hipEventCreate(&cl->ev[1]);
+  if (e != hipSuccess) {
+    sfmx_clean_destroy(ctx, cl);
+    return sfmx_fail(ctx, SFMX_ERR_HIP, "sfmx_clean_create", e);
+  }
+  *out = cl;
+  return SFMX_OK;
+}
+
+void sfmx_clean_destroy(sfmx_ctx* ctx, sfmx_clean* cl) {
+  if (!cl) return;
+  if (ctx) {
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+  for (DevBuf* b : {&cl->work, &cl->in_v, &cl->in_n, &cl->in_f, &cl->out_v, &cl->out_n, &cl->out_f, &cl->vsrc, &cl->fsrc}) b->release();
+  for (hipEvent_t ev : cl->ev)
+    if (ev) (void)hipEventDestroy(ev);
+  delete cl;
+}
+
+int sfmx_clean_run(sfmx_ctx* ctx, sfmx_clean* cl, const double* verts, const double* normals, int n, const int32_t* faces, int m,
+                   int on_device, const sfmx_clean_params* p, int* n_verts_out, int* n_faces_out, int* n_components, int* largest) {
+  cl_zero(n_verts_out, n_faces_out, n_components, largest);
+  SFMX_REQUIRE(ctx, ctx && cl);
+  cl->done = false;  // every failure from here on leaves no result behind
+  SFMX_REQUIRE(ctx, sfmx_clean_check_params(p) == SFMX_OK);
+  SFMX_REQUIRE(ctx, n >= 0 && m >= 0 && n < (1 << 30) && m < (1 << 30) && (n == 0 || verts) && (m == 0 || faces));
+  SFMX_HIP(ctx, hipSetDevice(ctx->device));
+  if (on_device) return cl_run(ctx, cl, verts, normals, n, faces, m, p, n_verts_out, n_faces_out, n_components, largest);
+  hipStream_t s = ctx->stream;
+  const size_t vb = (size_t)n * 24, fb = (size_t)m * 12;
+  SFMX_HIP(ctx, cl->in_v.ensure(vb));
+  SFMX_HIP(ctx, cl->in_f.ensure(fb));
+  if (n > 0) SFMX_HIP(ctx, hipMemcpyAsync(cl->in_v.p, verts, vb, hipMemcpyHostToDevice, s));
+  if (m > 0) SFMX_HIP(ctx, hipMemcpyAsync(cl->in_f.p, faces, fb, hipMemcpyHostToDevice, s));
+  if (normals) {
+    SFMX_HIP(ctx, cl->in_n.ensure(vb));
+    if (n > 0) SFMX_HIP(ctx, hipMemcpyAsync(cl->in_n.p, normals, vb, hipMemcpyHostToDevice, s));
+  }
+  return cl_run(ctx, cl, cl->in_v.as<double>(), normals ? cl->in_n.as<double>() : nullptr, n, cl->in_f.as<int32_t>(), m, p, n_verts_out,
+                n_faces_out, n_components, largest);
+}
+
+int sfmx_clean_fusion(sfmx_ctx* ctx, sfmx_clean* cl, const sfmx_fusion* fu, const sfmx_clean_params* p, int* n_verts_out,
+                      int* n_faces_out, int* n_components, int* largest) {
+  cl_zero(n_verts_out, n_faces_out, n_components, largest);
+  SFMX_REQUIRE(ctx, ctx && cl);
+  cl->done = false;  // every failure from here on leaves no result behind
+  SFMX_REQUIRE(ctx, fu && sfmx_clean_check_params(p) == SFMX_OK);
+  const double *v = nullptr, *nr = nullptr;
+  const int32_t* f = nullptr;
+  int m = 0;
+  const int n = sfmx_fusion_device_mesh(fu, &v, &nr, &f, &m);
+  SFMX_REQUIRE(ctx, n >= 0 && m >= 0);  // no current surface on the device
+  SFMX_HIP(ctx, hipSetDevice(ctx->device));
+  return cl_run(ctx, cl, v, nr, n, f, m, p, n_verts_out, n_faces_out, n_components, largest);
+}
+
+int sfmx_clean_read(sfmx_ctx* ctx, sfmx_clean* cl, double* verts_out, double* normals_out, int32_t* faces_out, int32_t* vert_src,
+                    int32_t* face_src, int32_t* vert_label, int32_t* vert_comp_faces) {
+  SFMX_REQUIRE(ctx, ctx && cl && cl->done);
+  SFMX_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t nv = (size_t)cl->nv_out, nf = (size_t)cl->nf_out, n = (size_t)cl->n;
+  if (verts_out && nv) SFMX_HIP(ctx, hipMemcpyAsync(verts_out, cl->out_v.p, nv * 24, hipMemcpyDeviceToHost, s));
+  if (normals_out && nv && cl->has_normals) SFMX_HIP(ctx, hipMemcpyAsync(normals_out, cl->out_n.p, nv * 24, hipMemcpyDeviceToHost, s));
+  if (faces_out && nf) SFMX_HIP(ctx, hipMemcpyAsync(faces_out, cl->out_f.p, nf * 12, hipMemcpyDeviceToHost, s));
+  if (vert_src && nv) SFMX_HIP(ctx, hipMemcpyAsync(vert_src, cl->vsrc.p, nv * 4, hipMemcpyDeviceToHost, s));
+  if (face_src && nf) SFMX_HIP(ctx, hipMemcpyAsync(face_src, cl->fsrc.p, nf * 4, hipMemcpyDeviceToHost, s));
+  if (vert_label && n) SFMX_HIP(ctx, hipMemcpyAsync(vert_label, cl->lab, n * 4, hipMemcpyDeviceToHost, s));
+  if (vert_comp_faces && n) SFMX_HIP(ctx, hipMemcpyAsync(vert_comp_faces, cl->vcf, n * 4, hipMemcpyDeviceToHost, s));
+  SFMX_HIP(ctx, hipStreamSynchronize(s));
+  return SFMX_OK;
+}
+
+int sfmx_clean_sizes(const sfmx_clean* cl, int* n, int* m, int* n_verts_out, int* n_faces_out) {
+  cl_zero(n, m, n_verts_out, n_faces_out);
+  if (!cl || !cl->done) return SFMX_ERR_INVALID;
+  if (n) *n = cl->n;
+  if (m) *m = cl->m;
+  if (n_verts_out) *n_verts_out = cl->nv_out;
+  if (n_faces_out) *n_faces_out = cl->nf_out;
+  return SFMX_OK;
+}
+
+int sfmx_clean_device_surface(const sfmx_clean* cl, const double** verts, const double** normals) {
+  if (verts) *verts = nullptr;
+  if (normals) *normals = nullptr;
+  if (!cl || !cl->done) return -1;
+  if (verts) *verts = cl->out_v.as<double>();
+  if (normals && cl->has_normals) *normals = cl->out_n.as<double>();
+  return cl->nv_out;
+}
+
+double sfmx_clean_last_us(const sfmx_clean* cl) { return cl ? cl->last_us : 0.0; }
+
+}  // extern "C"

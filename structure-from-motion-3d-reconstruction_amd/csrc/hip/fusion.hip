@@ -380,6 +380,8 @@ struct sfmx_fusion {
   // the last sfmx_fusion_extract_normals: normals next to out_v, and how many vertices of both are current (-1: none)
   DevBuf out_n;
   int resident = -1;
+  // vertices / faces of out_v / out_f that are the volume's current surface (-1: none), whichever extraction wrote them
+  int cur_v = -1, cur_f = -1;
   hipEvent_t ev[6] = {};
   double last_us = 0.0, normals_us = 0.0;
 };
@@ -544,6 +546,7 @@ int sfmx_fusion_reset(sfmx_ctx* ctx, sfmx_fusion* fu) {
   fu->last_us = 0.0;
   fu->normals_us = 0.0;
   fu->resident = -1;
+  fu->cur_v = fu->cur_f = -1;
   return SFMX_OK;
 }
 
@@ -579,6 +582,7 @@ int sfmx_fusion_integrate(sfmx_ctx* ctx, sfmx_fusion* fu) {
   hipStream_t s = ctx->stream;
   const int nv = (int)fu->pending.size();
   fu->resident = -1;  // the volume changes: the surface kept on the device is no longer its surface
+  fu->cur_v = fu->cur_f = -1;
   SFMX_HIP(ctx, hipMemcpyAsync(fu->d_views, fu->pending.data(), sizeof(FuView) * (size_t)nv, hipMemcpyHostToDevice, s));
   const FuGrid g = fu_grid(fu);
   const int bx = (g.nx + 63) / 64, by = (g.ny + 3) / 4;
@@ -645,6 +649,7 @@ static int fu_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts_c
   SFMX_REQUIRE(ctx, verts && faces && verts_cap >= nvx && faces_cap >= nf && (!want_normals || normals));
   fu->resident = want_normals ? 0 : -1;  // out_v is rewritten below
   fu->normals_us = 0.0;
+  fu->cur_v = fu->cur_f = nf == 0 ? 0 : -1;  // no faces: no edge slot is used either (nvx == 0), an empty surface is current
   if (nf == 0) return SFMX_OK;
   SFMX_HIP(ctx, fu->out_v.ensure((size_t)nvx * 24));
   SFMX_HIP(ctx, fu->out_f.ensure((size_t)nf * 12));
@@ -664,6 +669,8 @@ static int fu_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts_c
     SFMX_HIP(ctx, hipMemcpyAsync(normals, fu->out_n.p, (size_t)nvx * 24, hipMemcpyDeviceToHost, s));
   }
   SFMX_HIP(ctx, hipStreamSynchronize(s));
+  fu->cur_v = nvx;
+  fu->cur_f = nf;
   if (want_normals) {
     fu->resident = nvx;
     float ms = 0.f;
@@ -691,4 +698,12 @@ int sfmx_fusion_device_surface(const sfmx_fusion* fu, const double** verts, cons
   *verts = fu->out_v.as<double>();
   *normals = fu->out_n.as<double>();
   return fu->resident;
+}
+
+int sfmx_fusion_device_mesh(const sfmx_fusion* fu, const double** verts, const double** normals, const int32_t** faces, int* n_faces) {
+  *verts = fu->out_v.as<double>();
+  *normals = fu->resident >= 0 && fu->resident == fu->cur_v ? fu->out_n.as<double>() : nullptr;
+  *faces = fu->out_f.as<int32_t>();
+  *n_faces = fu->cur_f;
+  return fu->cur_v;
 }

@@ -148,6 +148,10 @@ const uint8_t* sfmx_stereo_device_rect_left(const sfmx_stereo* st, int* w, int* 
 // fusion.hip: vertices and normals (double [n][3] each) of the last sfmx_fusion_extract_normals on the device; returns n, or -1
 // when there is none (never extracted, or the volume or the vertex buffer has changed since)
 int sfmx_fusion_device_surface(const sfmx_fusion* fu, const double** verts, const double** normals);
+// fusion.hip: the surface the last extraction with arrays left on the device (verts double [n][3], faces int32 [*n_faces][3],
+// normals double [n][3] or NULL when that extraction made none); returns n, or -1 when there is none (never extracted, or the
+// volume has changed since)
+int sfmx_fusion_device_mesh(const sfmx_fusion* fu, const double** verts, const double** normals, const int32_t** faces, int* n_faces);
 // consist.hip: view i as it was added and its filtered map on the device; false without a current result or with i out of range
 bool sfmx_consist_device_view(const sfmx_consist* cs, int i, sfmx_fusion_view* view, const int16_t** filtered);
 

@@ -40,6 +40,13 @@
 #pragma weak sfmx_consist_filter
 #pragma weak sfmx_consist_counts
 #pragma weak sfmx_fusion_add_consist_view
+#pragma weak sfmx_clean_check_params
+#pragma weak sfmx_clean_create
+#pragma weak sfmx_clean_destroy
+#pragma weak sfmx_clean_fusion
+#pragma weak sfmx_clean_read
+#pragma weak sfmx_clean_device_surface
+#pragma weak sfmx_shade_vertices
 
 namespace {
 
@@ -49,7 +56,9 @@ struct Guard {
   sfmx_fusion* fu = nullptr;
   sfmx_shade* sh = nullptr;
   sfmx_consist* cs = nullptr;
+  sfmx_clean* cl = nullptr;
   ~Guard() {
+    if (cl) sfmx_clean_destroy(ctx, cl);
     if (cs) sfmx_consist_destroy(ctx, cs);
     if (st) sfmx_stereo_destroy(ctx, st);
     if (fu) sfmx_fusion_destroy(ctx, fu);
@@ -129,6 +138,15 @@ int sfmx_host_fusion_mesh_cs(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
                              const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
                              int32_t* pair_counts, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_cl(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, nullptr, nullptr,
+                                  res, ply_path, warn, warn_cap);
+}
+
+int sfmx_host_fusion_mesh_cl(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, sfmx_fusion_result_ex* res,
+                             const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -136,6 +154,8 @@ int sfmx_host_fusion_mesh_cs(sfmx_ctx* ctx, const uint8_t* const* images, int on
   if (!&sfmx_fusion_create || !&sfmx_stereo_disparity) return SFMX_ERR_UNSUPPORTED;
   if (app && (!&sfmx_shade_create || !&sfmx_fusion_extract_normals)) return SFMX_ERR_UNSUPPORTED;
   if (cs && (!&sfmx_consist_create || !&sfmx_fusion_add_consist_view)) return SFMX_ERR_UNSUPPORTED;
+  if (clean && (!&sfmx_clean_create || !&sfmx_clean_fusion || !&sfmx_clean_read || !&sfmx_clean_device_surface || !&sfmx_shade_vertices))
+    return SFMX_ERR_UNSUPPORTED;
   int rc = sfmx_stereo_check_params(w, h, sp);
   if (rc != SFMX_OK) return rc;
   rc = sfmx_fusion_check_params(fp);
@@ -152,6 +172,12 @@ int sfmx_host_fusion_mesh_cs(sfmx_ctx* ctx, const uint8_t* const* images, int on
     if (rc != SFMX_OK) return rc;
     if (pair_counts)
       for (int q = 0; q < 2 * m; q++) pair_counts[q] = -1;
+  }
+  if (clean) {
+    rc = sfmx_clean_check_params(clean);
+    if (rc != SFMX_OK) return rc;
+    if (clean_counts)
+      for (int q = 0; q < 4; q++) clean_counts[q] = 0;
   }
   std::string log;
   Guard g{ctx};
@@ -234,6 +260,24 @@ int sfmx_host_fusion_mesh_cs(sfmx_ctx* ctx, const uint8_t* const* images, int on
   int nv = 0, nf = 0;
   rc = sfmx_fusion_extract(ctx, g.fu, nullptr, 0, nullptr, 0, &nv, &nf);
   if (rc != SFMX_OK) return rc;
+  if (clean && nf > 0) {
+    // the extraction always returns its arrays to the host; the cleaning reads the copy it left on the device
+    const int nv0 = nv, nf0 = nf;
+    std::vector<double> tv((size_t)nv * 3), tn(app ? (size_t)nv * 3 : 0);
+    std::vector<int32_t> tf((size_t)nf * 3);
+    rc = app ? sfmx_fusion_extract_normals(ctx, g.fu, tv.data(), nv, tf.data(), nf, tn.data(), &nv, &nf)
+             : sfmx_fusion_extract(ctx, g.fu, tv.data(), nv, tf.data(), nf, &nv, &nf);
+    if (rc == SFMX_OK) rc = sfmx_clean_create(ctx, &g.cl);
+    int ncomp = 0, largest = 0;
+    if (rc == SFMX_OK) rc = sfmx_clean_fusion(ctx, g.cl, g.fu, clean, &nv, &nf, &ncomp, &largest);
+    if (rc != SFMX_OK) return rc;
+    if (clean_counts) {
+      clean_counts[0] = ncomp;
+      clean_counts[1] = largest;
+      clean_counts[2] = nv0 - nv;
+      clean_counts[3] = nf0 - nf;
+    }
+  }
   if (nf > 0) {
     res->verts = static_cast<double*>(std::malloc((size_t)nv * 3 * sizeof(double)));
     res->faces = static_cast<int32_t*>(std::malloc((size_t)nf * 3 * sizeof(int32_t)));
@@ -248,7 +292,14 @@ int sfmx_host_fusion_mesh_cs(sfmx_ctx* ctx, const uint8_t* const* images, int on
       res->n_views = keep;
       return SFMX_ERR_INVALID;
     }
-    if (app) {
+    if (clean) {
+      rc = sfmx_clean_read(ctx, g.cl, res->verts, res->normals, res->faces, nullptr, nullptr, nullptr, nullptr);
+      if (rc == SFMX_OK && app) {  // per vertex: the uncleaned shading gathered by vert_src
+        const double *dv = nullptr, *dn = nullptr;
+        rc = sfmx_clean_device_surface(g.cl, &dv, &dn) == nv ? SFMX_OK : SFMX_ERR_INVALID;
+        if (rc == SFMX_OK) rc = sfmx_shade_vertices(ctx, g.sh, dv, dn, nv, 1, &ap, res->grey, res->views);
+      }
+    } else if (app) {
       rc = sfmx_fusion_extract_normals(ctx, g.fu, res->verts, nv, res->faces, nf, res->normals, &nv, &nf);
       if (rc == SFMX_OK) rc = sfmx_shade_fusion(ctx, g.sh, g.fu, &ap, res->grey, res->views);
     } else {

@@ -52,4 +52,16 @@ int sfmx_host_fusion_mesh_cs(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
                              const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
                              int32_t* pair_counts, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_cs with the small connected components of the surface removed.  clean = NULL: exactly
+// sfmx_host_fusion_mesh_cs (clean_counts is not touched).  Otherwise the surface is extracted (with normals when app is given),
+// cleaned on the device (sfmx_clean_fusion), and with app the CLEANED device vertices and normals are shaded; the result arrays
+// and the PLY are the cleaned mesh.  clean_counts (optional) int32 [4]: components, faces of the largest, vertices removed,
+// faces removed.  A surface whose every component falls below min_faces has no faces left (the PLY is then skipped with its
+// WARN line).
+int sfmx_host_fusion_mesh_cl(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, sfmx_fusion_result_ex* res,
+                             const char* ply_path, char* warn, int warn_cap);
 }

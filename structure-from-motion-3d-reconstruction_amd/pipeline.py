@@ -182,6 +182,7 @@ class FusionResultEx(ctypes.Structure):
 
 APPEARANCE_KEYS = ("depth_tol", "cull", "fill")
 CONSISTENCY_KEYS = ("rel_tol", "reproj_px", "min_support")
+CLEAN_KEYS = ("min_faces", "min_permille")
 
 
 def _split_fusion_params(params: dict):
@@ -193,7 +194,7 @@ def _split_fusion_params(params: dict):
 
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
-         consistency=False, **params) -> dict:
+         consistency=False, clean=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -205,7 +206,10 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     consistency: True, or dict(rel_tol=, reproj_px=, min_support=) (disp_min is the fusion's) -- every pair's disparity map is
     filtered against the other pairs' before it enters the volume: the dict gains consistency =
     dict(valid=[...], kept=[...]), the valid and the kept pixels of each integrated pair.  The shade views of appearance keep
-    the unfiltered maps."""
+    the unfiltered maps.
+    clean: True, or dict(min_faces=, min_permille=) -- the small connected components of the extracted surface are removed on
+    the device before the arrays and the PLY are made; with appearance the cleaned vertices are shaded.  The dict
+    gains clean = dict(components=, largest=, verts_removed=, faces_removed=)."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -226,7 +230,7 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     K = np.ascontiguousarray(K, np.float64).reshape(9)
     warn = ctypes.create_string_buffer(1 << 16)
     dp = POINTER(c_double)
-    ap = cp = counts = None
+    ap = cp = counts = lp = None
     if appearance:
         akw = {} if appearance is True else dict(appearance)
         unknown = set(akw) - set(APPEARANCE_KEYS)
@@ -240,12 +244,23 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             raise TypeError(f"unknown consistency parameters {sorted(unknown)}")
         cp = capi.consist_params(disp_min=fp.disp_min, **ckw)
         counts = np.full((max(len(pr), 1), 2), -1, np.int32)
-    if ap is not None or cp is not None:
+    if clean:
+        lkw = {} if clean is True else dict(clean)
+        unknown = set(lkw) - set(CLEAN_KEYS)
+        if unknown:
+            raise TypeError(f"unknown clean parameters {sorted(unknown)}")
+        lp = capi.clean_params(**lkw)
+        lcounts = np.zeros(4, np.int32)
+    if ap is not None or cp is not None or lp is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if cp is not None:
+        if lp is not None:
+            rc = lib.sfmx_host_fusion_mesh_cl(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None, byref(lp),
+                                              lcounts.ctypes.data_as(POINTER(c_int)), *tail)
+        elif cp is not None:
             rc = lib.sfmx_host_fusion_mesh_cs(*head, byref(cp), counts.ctypes.data_as(POINTER(c_int)), *tail)
         else:
             rc = lib.sfmx_host_fusion_mesh_ex(*head, *tail)
@@ -265,6 +280,8 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         if cp is not None:
             done = counts[:len(pr)][counts[:len(pr), 0] >= 0]
             out["consistency"] = dict(valid=[int(v) for v in done[:, 0]], kept=[int(v) for v in done[:, 1]])
+        if lp is not None:
+            out["clean"] = dict(zip(("components", "largest", "verts_removed", "faces_removed"), (int(v) for v in lcounts)))
         return out
     res = FusionResult()
     rc = lib.sfmx_host_fusion_mesh(ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp),
@@ -310,7 +327,8 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     fusion (optional): {'pairs': [(a, b), ...], 'origin', 'voxel', 'dims', **params} (keyframe indices; params as fuse) -- after
     the run, fuse() on the run's own keyframe frames and kf_poses: the result gains fused_mesh = fuse()'s dict, and out_dir
     gains templeRing_mesh_fused.ply; 'appearance' (True or a dict, as fuse) adds normals and vertex grey to both;
-    'consistency' (True or a dict, as fuse) filters the pairs' disparity maps against each other first.  The run itself, its log and every other output are unchanged.
+    'consistency' (True or a dict, as fuse) filters the pairs' disparity maps against each other first; 'clean' (True or a
+    dict, as fuse) removes the surface's small connected components.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -373,8 +391,9 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         ply = os.path.join(out_dir, "templeRing_mesh_fused.ply") if out_dir else None
         appearance = fz.pop("appearance", False)
         consistency = fz.pop("consistency", False)
+        clean = fz.pop("clean", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
-                                 appearance=appearance, consistency=consistency, **fz)
+                                 appearance=appearance, consistency=consistency, clean=clean, **fz)
     return out
 
 

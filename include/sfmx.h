@@ -455,6 +455,55 @@ int sfmx_clean_device_surface(const sfmx_clean* cl, const double** verts, const 
 /* device time (us) of the launches of the last sfmx_clean_run / _fusion when timing is on (sfmx_set_timing), else 0 */
 double sfmx_clean_last_us(const sfmx_clean* cl);
 
+/* ---- distance from points to the nearest point of a triangle mesh ------------------------------------------ */
+/* For each query p: d2 = the smallest squared point-triangle distance over the faces whose bounding box, grown by
+ * d_max (1 + 2^-10) on every side, holds p, and face = the smallest index of a face attaining it; when there is no such face
+ * or !(d2 < d_max^2), d2 = d_max^2 and face = -1.  The point-triangle distance is one fixed sequence of IEEE double operations
+ * (csrc/hip/sfmx_sdist_math.h), and a minimum does not depend on the order of its candidates: d2 and face are bit-identical to
+ * the brute-force NumPy restatement in tests/sdist_ref.py for every cell size.  The distance itself is sqrt(d2), taken by
+ * the caller.  The uniform grid behind it only changes the speed. */
+#define SFMX_SDIST_CHUNK 64 /* triangles of a cell staged through LDS at a time */
+typedef struct sfmx_sdist sfmx_sdist;  /* a copy of the target mesh, its grid and the work buffers; they grow on demand and are kept */
+typedef struct sfmx_sdist_params {
+  double d_max;  /* distances are clipped here; 2^-500 <= d_max <= 2^60 (its square neither underflows nor, with the coordinate
+                  * limit below, does a distance overflow); no default (a length in the caller's units) */
+  double cell;   /* edge of a grid cell; 0 (default): 2 d_max, doubled until the grid has <= 2^24 cells and <= 2^30 entries */
+} sfmx_sdist_params;
+void sfmx_sdist_default_params(sfmx_sdist_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_sdist_check_params(const sfmx_sdist_params* p);
+int sfmx_sdist_create(sfmx_ctx* ctx, sfmx_sdist** out);
+void sfmx_sdist_destroy(sfmx_ctx* ctx, sfmx_sdist* sd);
+/* verts double [nv][3], faces int32 [m][3]; host pointers or (on_device = 1) device pointers, copied; 0 <= nv, m < 2^30.
+ * SFMX_ERR_INVALID (found on the device, nothing is read through a bad index) for a face index outside [0, nv), a non-finite
+ * coordinate in a vertex that a face uses, a coordinate beyond 2^40 d_max in magnitude, or an explicit cell that does not fit
+ * the two limits above.  A failed call leaves no target; the object stays usable.  m = 0 is a valid target (every query is
+ * clipped).  Faces with repeated indices and collinear faces are allowed: their distance is that of their segments. */
+int sfmx_sdist_set_target(sfmx_ctx* ctx, sfmx_sdist* sd, const double* verts, int nv, const int32_t* faces, int m, int on_device,
+                          const sfmx_sdist_params* p);
+/* the same for the surface the last sfmx_fusion_extract / _extract_normals with arrays left on the device inside fu, and for
+ * the cleaned surface of the last successful run on cl (no host round trip); SFMX_ERR_INVALID when there is none */
+int sfmx_sdist_set_target_fusion(sfmx_ctx* ctx, sfmx_sdist* sd, const sfmx_fusion* fu, const sfmx_sdist_params* p);
+int sfmx_sdist_set_target_clean(sfmx_ctx* ctx, sfmx_sdist* sd, const sfmx_clean* cl, const sfmx_sdist_params* p);
+/* points double [n][3], a host pointer or (on_device = 1) a device pointer; d2_out double [n] and face_out int32 [n] on the
+ * host, either may be NULL.  n = 0 is not an error.  SFMX_ERR_INVALID before a successful set_target, and for a non-finite
+ * coordinate in a query (the target stays). */
+int sfmx_sdist_query(sfmx_ctx* ctx, sfmx_sdist* sd, const double* points, int n, int on_device, double* d2_out, int32_t* face_out);
+/* the same with the vertices of that device surface as queries.  The outputs hold cap entries each; a surface with more
+ * vertices is refused (SFMX_ERR_INVALID, nothing written) unless both outputs are NULL.  *n_out (may be NULL) = its vertex
+ * count, 0 on failure. */
+int sfmx_sdist_query_fusion(sfmx_ctx* ctx, sfmx_sdist* sd, const sfmx_fusion* fu, int cap, double* d2_out, int32_t* face_out,
+                            int* n_out);
+int sfmx_sdist_query_clean(sfmx_ctx* ctx, sfmx_sdist* sd, const sfmx_clean* cl, int cap, double* d2_out, int32_t* face_out,
+                           int* n_out);
+/* of the current target: dims3 int [3] (cells per axis, zeros for a target without faces), entries (triangle-cell pairs), the
+ * cell size used; tests = point-triangle pairs the last query visited (an integer counter on the device); kernel_us = the device
+ * time (us) of the query kernel alone inside the last query when timing is on, else 0 (the rest of sfmx_sdist_last_us is the
+ * binning).  Any may be NULL.  SFMX_ERR_INVALID (and zeros) without a target; needs no context. */
+int sfmx_sdist_stats(const sfmx_sdist* sd, int* dims3, int* entries, double* cell, uint64_t* tests, double* kernel_us);
+/* device time (us) from the first to the last launch of the last sfmx_sdist_set_target* / _query* when timing is on, else 0 */
+double sfmx_sdist_last_us(const sfmx_sdist* sd);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

@@ -44,6 +44,9 @@ SYMBOLS = [
     "sfmx_consist_counts", "sfmx_fusion_add_consist_view", "sfmx_consist_last_us",
     "sfmx_clean_default_params", "sfmx_clean_check_params", "sfmx_clean_create", "sfmx_clean_destroy", "sfmx_clean_run",
     "sfmx_clean_fusion", "sfmx_clean_read", "sfmx_clean_sizes", "sfmx_clean_device_surface", "sfmx_clean_last_us",
+    "sfmx_sdist_default_params", "sfmx_sdist_check_params", "sfmx_sdist_create", "sfmx_sdist_destroy", "sfmx_sdist_set_target",
+    "sfmx_sdist_set_target_fusion", "sfmx_sdist_set_target_clean", "sfmx_sdist_query", "sfmx_sdist_query_fusion",
+    "sfmx_sdist_query_clean", "sfmx_sdist_stats", "sfmx_sdist_last_us",
 ]
 
 
@@ -204,6 +207,30 @@ def clean_check_params(**kw) -> bool:
     return load_library().sfmx_clean_check_params(byref(clean_params(**kw))) == SFMX_OK
 
 
+class SdistParams(ctypes.Structure):
+    _fields_ = [("d_max", c_double), ("cell", c_double)]
+
+
+SDIST_CHUNK = 64  # SFMX_SDIST_CHUNK: triangles of a cell staged through LDS at a time
+
+
+def sdist_params(d_max, cell=0.0) -> SdistParams:
+    """d_max has no default (a length in the caller's units); cell 0 = auto"""
+    return SdistParams(float(d_max), float(cell))
+
+
+def sdist_default_params() -> dict:
+    """sfmx_sdist_default_params as a dict (needs no device)"""
+    p = SdistParams()
+    load_library().sfmx_sdist_default_params(byref(p))
+    return dict(d_max=p.d_max, cell=p.cell)
+
+
+def sdist_check_params(d_max, cell=0.0) -> bool:
+    """True if sfmx_sdist_set_target would accept the parameters; needs no device"""
+    return load_library().sfmx_sdist_check_params(byref(sdist_params(d_max, cell))) == SFMX_OK
+
+
 def stereo_check_params(w: int, h: int, **kw) -> bool:
     """True if sfmx_stereo_create would accept (w, h, params); needs no device"""
     return load_library().sfmx_stereo_check_params(c_int(w), c_int(h), byref(stereo_params(**kw))) == SFMX_OK
@@ -236,6 +263,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_shade_last_us.restype = c_double
         _lib.sfmx_consist_last_us.restype = c_double
         _lib.sfmx_clean_last_us.restype = c_double
+        _lib.sfmx_sdist_last_us.restype = c_double
     return _lib
 
 
@@ -605,6 +633,98 @@ class Clean:
             pass
 
 
+class Sdist:
+    """sfmx_sdist: squared distance from points to the nearest point of a target triangle mesh.  One target
+    serves many query sets; the target's grid and the work buffers are kept between calls."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_sdist_create(ctx.h_, byref(self.h_)))
+
+    def set_target(self, verts, faces, d_max, cell=0.0, nv=None, m=None):
+        """verts float64 [nv][3] and faces int32 [m][3]: numpy arrays, or ints (device pointers) with nv and m given"""
+        p = sdist_params(d_max, cell)
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int):
+            raise TypeError("verts and faces: both host arrays or both device pointers")
+        if on_dev:
+            pv, pf = c_void_p(verts), c_void_p(faces)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            nv, m = len(verts), len(faces)
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+        self.ctx._chk(self.ctx.lib.sfmx_sdist_set_target(self.ctx.h_, self.h_, pv, c_int(nv), pf, c_int(m), c_int(1 if on_dev else 0),
+                                                         byref(p)))
+
+    def set_target_fusion(self, fu: "Fusion", d_max, cell=0.0):
+        """the surface fu.extract() / fu.extract_normals() left on the device"""
+        p = sdist_params(d_max, cell)
+        self.ctx._chk(self.ctx.lib.sfmx_sdist_set_target_fusion(self.ctx.h_, self.h_, fu.h_, byref(p)))
+
+    def set_target_clean(self, cl: "Clean", d_max, cell=0.0):
+        """the cleaned surface of cl's last run, on the device"""
+        p = sdist_params(d_max, cell)
+        self.ctx._chk(self.ctx.lib.sfmx_sdist_set_target_clean(self.ctx.h_, self.h_, cl.h_, byref(p)))
+
+    def query(self, points, n=None):
+        """points float64 [n][3]: a numpy array, or an int (device pointer) with n given.  Returns (d2 f64 [n], face i32 [n]):
+        the squared distance clipped at d_max^2 and the nearest face (-1 where clipped)."""
+        on_dev = isinstance(points, int)
+        if on_dev:
+            pp = c_void_p(points)
+        else:
+            points = _f64(points).reshape(-1, 3)
+            n = len(points)
+            pp = points.ctypes.data_as(c_void_p)
+        d2, face = np.zeros(max(n, 1)), np.zeros(max(n, 1), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_sdist_query(self.ctx.h_, self.h_, pp, c_int(n), c_int(1 if on_dev else 0), _p(d2, c_double),
+                                                    _p(face, c_int32)))
+        return d2[:n].copy(), face[:n].copy()
+
+    def _query_surface(self, fn, obj, cap):
+        """the library says how many vertices the device surface has; a surface larger than cap is refused, not written"""
+        d2, face, n = np.zeros(max(cap, 1)), np.zeros(max(cap, 1), np.int32), c_int(0)
+        self.ctx._chk(fn(self.ctx.h_, self.h_, obj.h_, c_int(cap), _p(d2, c_double), _p(face, c_int32), byref(n)))
+        return d2[:n.value].copy(), face[:n.value].copy()
+
+    def query_fusion(self, fu: "Fusion", n=None):
+        """the vertices fu.extract() / fu.extract_normals() left on the device as queries; n (optional): the count the caller
+        expects, at most that many are accepted (default: fu.counts())"""
+        return self._query_surface(self.ctx.lib.sfmx_sdist_query_fusion, fu, fu.counts()[0] if n is None else int(n))
+
+    def query_clean(self, cl: "Clean"):
+        """the cleaned vertices of cl's last run, on the device, as queries"""
+        return self._query_surface(self.ctx.lib.sfmx_sdist_query_clean, cl, cl.sizes()[2])
+
+    def stats(self) -> dict:
+        """dict(dims (cells per axis), cells, entries (triangle-cell pairs), cell (the size used), tests (point-triangle pairs
+        the last query visited), kernel_us (the query kernel alone inside the last query, when timing is on), chunk (triangles
+        staged through LDS at a time)); raises without a target"""
+        dims, ent, cell, tests, kus = (c_int * 3)(), c_int(0), c_double(0.0), c_uint64(0), c_double(0.0)
+        rc = self.ctx.lib.sfmx_sdist_stats(self.h_, dims, byref(ent), byref(cell), byref(tests), byref(kus))
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_sdist_stats: no target")
+        d = tuple(int(v) for v in dims)
+        return dict(dims=d, cells=d[0] * d[1] * d[2], entries=int(ent.value), cell=float(cell.value), tests=int(tests.value),
+                    kernel_us=float(kus.value), chunk=SDIST_CHUNK)
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_sdist_last_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_sdist_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Stereo:
     """Device buffers of sfmx_stereo for one (w, h, params); disparity() runs rectify -> census -> SGM -> select -> speckle."""
 
@@ -941,6 +1061,9 @@ class Context:
 
     def clean(self) -> "Clean":
         return Clean(self)
+
+    def sdist(self) -> "Sdist":
+        return Sdist(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

@@ -445,3 +445,14 @@ int sfmx_clean_device_surface(const sfmx_clean* cl, const double** verts, const 
 double sfmx_clean_last_us(const sfmx_clean* cl) { return cl ? cl->last_us : 0.0; }
 
 }  // extern "C"
+
+int sfmx_clean_device_mesh(const sfmx_clean* cl, const double** verts, const int32_t** faces, int* n_faces) {
+  *verts = nullptr;
+  *faces = nullptr;
+  *n_faces = 0;
+  if (!cl || !cl->done) return -1;
+  *verts = cl->out_v.as<double>();
+  *faces = cl->out_f.as<int32_t>();
+  *n_faces = cl->nf_out;
+  return cl->nv_out;
+}

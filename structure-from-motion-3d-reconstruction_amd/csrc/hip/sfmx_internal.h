@@ -152,6 +152,9 @@ int sfmx_fusion_device_surface(const sfmx_fusion* fu, const double** verts, cons
 // normals double [n][3] or NULL when that extraction made none); returns n, or -1 when there is none (never extracted, or the
 // volume has changed since)
 int sfmx_fusion_device_mesh(const sfmx_fusion* fu, const double** verts, const double** normals, const int32_t** faces, int* n_faces);
+// clean.hip: the cleaned mesh of the last successful run on the device (verts double [n'][3], faces int32 [*n_faces][3]);
+// returns n', or -1 before a successful run
+int sfmx_clean_device_mesh(const sfmx_clean* cl, const double** verts, const int32_t** faces, int* n_faces);
 // consist.hip: view i as it was added and its filtered map on the device; false without a current result or with i out of range
 bool sfmx_consist_device_view(const sfmx_consist* cs, int i, sfmx_fusion_view* view, const int16_t** filtered);
 

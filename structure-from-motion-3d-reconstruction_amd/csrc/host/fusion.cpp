@@ -2,7 +2,9 @@
 // rectified view with its device disparity map; then one integration and one extraction.
 #include "fusion.hpp"
 
+#include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,6 +49,15 @@
 #pragma weak sfmx_clean_read
 #pragma weak sfmx_clean_device_surface
 #pragma weak sfmx_shade_vertices
+#pragma weak sfmx_sdist_check_params
+#pragma weak sfmx_sdist_create
+#pragma weak sfmx_sdist_destroy
+#pragma weak sfmx_sdist_set_target
+#pragma weak sfmx_sdist_set_target_fusion
+#pragma weak sfmx_sdist_set_target_clean
+#pragma weak sfmx_sdist_query
+#pragma weak sfmx_sdist_query_fusion
+#pragma weak sfmx_sdist_query_clean
 
 namespace {
 
@@ -57,7 +68,9 @@ struct Guard {
   sfmx_shade* sh = nullptr;
   sfmx_consist* cs = nullptr;
   sfmx_clean* cl = nullptr;
+  sfmx_sdist* sd = nullptr;
   ~Guard() {
+    if (sd) sfmx_sdist_destroy(ctx, sd);
     if (cl) sfmx_clean_destroy(ctx, cl);
     if (cs) sfmx_consist_destroy(ctx, cs);
     if (st) sfmx_stereo_destroy(ctx, st);
@@ -93,9 +106,107 @@ void write_mesh_ply_appearance(const std::string& path, const sfmx_fusion_result
   for (int i = 0; i < r.n_faces; i++) f << "3 " << r.faces[3 * i] << " " << r.faces[3 * i + 1] << " " << r.faces[3 * i + 2] << "\n";
 }
 
+bool sdist_linked() {
+  return &sfmx_sdist_check_params && &sfmx_sdist_create && &sfmx_sdist_destroy && &sfmx_sdist_set_target && &sfmx_sdist_set_target_fusion &&
+         &sfmx_sdist_set_target_clean && &sfmx_sdist_query && &sfmx_sdist_query_fusion && &sfmx_sdist_query_clean;
+}
+
+int check_eval_params(const sfmx_surface_eval_params* p) {
+  if (!p) return SFMX_ERR_INVALID;
+  const sfmx_sdist_params sp{p->d_max, p->cell};
+  if (sfmx_sdist_check_params(&sp) != SFMX_OK) return SFMX_ERR_INVALID;
+  if (!(p->tau >= 0.0) || !(p->tau <= p->d_max)) return SFMX_ERR_INVALID;
+  if (!(p->percentile > 0.0) || !(p->percentile <= 100.0)) return SFMX_ERR_INVALID;
+  return SFMX_OK;
+}
+
+// 1 per vertex that a face uses; false when a face index is outside [0, nv)
+bool used_mask(const int32_t* faces, int m, int nv, std::vector<uint8_t>& used) {
+  used.assign((size_t)nv, 0);
+  for (size_t q = 0; q < (size_t)m * 3; q++) {
+    if (faces[q] < 0 || faces[q] >= nv) return false;
+    used[(size_t)faces[q]] = 1;
+  }
+  return true;
+}
+
+// the statistics of one direction from the squared distances of the used vertices, in index order
+void eval_side(const std::vector<double>& d2, const std::vector<uint8_t>* used, const sfmx_surface_eval_params& p, int* n_out, int* within,
+               double* rank, double* mean, double* mx) {
+  std::vector<double> d;
+  d.reserve(d2.size());
+  for (size_t i = 0; i < d2.size(); i++)
+    if (!used || (*used)[i]) d.push_back(std::sqrt(d2[i]));
+  const long long n = (long long)d.size();
+  int w = 0;
+  double sum = 0.0, top = 0.0;
+  for (double x : d) {  // one sequential sum in index order
+    w += x <= p.tau ? 1 : 0;
+    sum += x;
+    top = x > top ? x : top;
+  }
+  *n_out = (int)n;
+  *within = w;
+  if (!rank) return;
+  const double nan = std::nan("");
+  *rank = *mean = *mx = nan;
+  if (n == 0) return;
+  *mean = sum / (double)n;
+  *mx = top;
+  // nearest rank, as the stereo mesh's depth cap: sorted(d)[ceil(p/100 n) - 1]
+  const long long k = std::min(std::max((long long)std::ceil(p.percentile / 100.0 * (double)n), 1LL), n);
+  std::nth_element(d.begin(), d.begin() + (k - 1), d.end());
+  *rank = d[(size_t)(k - 1)];
+}
+
+void eval_finish(sfmx_surface_eval_result* r) {
+  r->completeness = r->n_gt > 0 ? (double)r->comp_within / (double)r->n_gt : std::nan("");
+}
+
+std::vector<double> compact(const double* v, const std::vector<uint8_t>& used) {
+  std::vector<double> out;
+  for (size_t i = 0; i < used.size(); i++)
+    if (used[i]) out.insert(out.end(), v + 3 * i, v + 3 * i + 3);
+  return out;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sfmx_host_surface_eval(sfmx_ctx* ctx, const double* rec_verts, int n_rec_verts, const int32_t* rec_faces, int n_rec_faces,
+                           const double* gt_verts, int n_gt_verts, const int32_t* gt_faces, int n_gt_faces,
+                           const sfmx_surface_eval_params* p, sfmx_surface_eval_result* out) {
+  if (!ctx || !out || n_rec_verts < 0 || n_rec_faces < 0 || n_gt_verts < 0 || n_gt_faces < 0 || (n_rec_verts > 0 && !rec_verts) ||
+      (n_rec_faces > 0 && !rec_faces) || (n_gt_verts > 0 && !gt_verts) || (n_gt_faces > 0 && !gt_faces))
+    return SFMX_ERR_INVALID;
+  *out = sfmx_surface_eval_result{};
+  if (!sdist_linked()) return SFMX_ERR_UNSUPPORTED;
+  int rc = check_eval_params(p);
+  if (rc != SFMX_OK) return rc;
+  std::vector<uint8_t> ru, gu;
+  if (!used_mask(rec_faces, n_rec_faces, n_rec_verts, ru) || !used_mask(gt_faces, n_gt_faces, n_gt_verts, gu)) return SFMX_ERR_INVALID;
+  const std::vector<double> rq = compact(rec_verts, ru), gq = compact(gt_verts, gu);
+  const sfmx_sdist_params sp{p->d_max, p->cell};
+  Guard g{ctx};
+  rc = sfmx_sdist_create(ctx, &g.sd);
+  if (rc != SFMX_OK) return rc;
+  std::vector<double> d2(rq.size() / 3);
+  rc = sfmx_sdist_set_target(ctx, g.sd, gt_verts, n_gt_verts, gt_faces, n_gt_faces, 0, &sp);
+  if (rc == SFMX_OK) rc = sfmx_sdist_query(ctx, g.sd, rq.data(), (int)d2.size(), 0, d2.data(), nullptr);
+  if (rc != SFMX_OK) return rc;
+  eval_side(d2, nullptr, *p, &out->n_rec, &out->acc_within, &out->accuracy, &out->acc_mean, &out->acc_max);
+  d2.assign(gq.size() / 3, 0.0);
+  rc = sfmx_sdist_set_target(ctx, g.sd, rec_verts, n_rec_verts, rec_faces, n_rec_faces, 0, &sp);
+  if (rc == SFMX_OK) rc = sfmx_sdist_query(ctx, g.sd, gq.data(), (int)d2.size(), 0, d2.data(), nullptr);
+  if (rc != SFMX_OK) {
+    *out = sfmx_surface_eval_result{};
+    return rc;
+  }
+  eval_side(d2, nullptr, *p, &out->n_gt, &out->comp_within, nullptr, nullptr, nullptr);
+  eval_finish(out);
+  return SFMX_OK;
+}
 
 void sfmx_host_fusion_free_ex(sfmx_fusion_result_ex* res) {
   if (!res) return;
@@ -147,6 +258,15 @@ int sfmx_host_fusion_mesh_cl(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
                              int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, sfmx_fusion_result_ex* res,
                              const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_ev(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts,
+                                  nullptr, nullptr, res, ply_path, warn, warn_cap);
+}
+
+int sfmx_host_fusion_mesh_ev(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -156,10 +276,19 @@ int sfmx_host_fusion_mesh_cl(sfmx_ctx* ctx, const uint8_t* const* images, int on
   if (cs && (!&sfmx_consist_create || !&sfmx_fusion_add_consist_view)) return SFMX_ERR_UNSUPPORTED;
   if (clean && (!&sfmx_clean_create || !&sfmx_clean_fusion || !&sfmx_clean_read || !&sfmx_clean_device_surface || !&sfmx_shade_vertices))
     return SFMX_ERR_UNSUPPORTED;
+  if (gt && !sdist_linked()) return SFMX_ERR_UNSUPPORTED;
   int rc = sfmx_stereo_check_params(w, h, sp);
   if (rc != SFMX_OK) return rc;
   rc = sfmx_fusion_check_params(fp);
   if (rc != SFMX_OK) return rc;
+  std::vector<uint8_t> gt_used;
+  if (gt) {
+    if (!ev || gt->n_verts < 0 || gt->n_faces < 0 || (gt->n_verts > 0 && !gt->verts) || (gt->n_faces > 0 && !gt->faces)) return SFMX_ERR_INVALID;
+    *ev = sfmx_surface_eval_result{};
+    rc = check_eval_params(&gt->params);
+    if (rc != SFMX_OK) return rc;
+    if (!used_mask(gt->faces, gt->n_faces, gt->n_verts, gt_used)) return SFMX_ERR_INVALID;
+  }
   sfmx_shade_params ap{};
   if (app) {
     ap = *app;
@@ -313,6 +442,40 @@ int sfmx_host_fusion_mesh_cl(sfmx_ctx* ctx, const uint8_t* const* images, int on
     }
     res->n_verts = nv;
     res->n_faces = nf;
+  }
+  if (gt) {
+    // the final mesh is still on the device (inside the clean object, or inside the volume after the last extraction): it is
+    // the query set of the accuracy and the target of the completeness, with no host round trip
+    const sfmx_sdist_params dp{gt->params.d_max, gt->params.cell};
+    const std::vector<double> gq = compact(gt->verts, gt_used);
+    std::vector<uint8_t> used;
+    std::vector<double> d2((size_t)(nf > 0 ? nv : 0));
+    rc = sfmx_sdist_create(ctx, &g.sd);
+    if (rc == SFMX_OK) rc = sfmx_sdist_set_target(ctx, g.sd, gt->verts, gt->n_verts, gt->faces, gt->n_faces, 0, &dp);
+    if (rc == SFMX_OK && nf > 0) {
+      rc = used_mask(res->faces, nf, nv, used) ? SFMX_OK : SFMX_ERR_INVALID;
+      if (rc == SFMX_OK)
+        rc = clean ? sfmx_sdist_query_clean(ctx, g.sd, g.cl, nv, d2.data(), nullptr, nullptr)
+                   : sfmx_sdist_query_fusion(ctx, g.sd, g.fu, nv, d2.data(), nullptr, nullptr);
+    }
+    if (rc == SFMX_OK) {
+      eval_side(d2, &used, gt->params, &ev->n_rec, &ev->acc_within, &ev->accuracy, &ev->acc_mean, &ev->acc_max);
+      d2.assign(gq.size() / 3, 0.0);
+      if (nf == 0)
+        rc = sfmx_sdist_set_target(ctx, g.sd, nullptr, 0, nullptr, 0, 0, &dp);
+      else
+        rc = clean ? sfmx_sdist_set_target_clean(ctx, g.sd, g.cl, &dp) : sfmx_sdist_set_target_fusion(ctx, g.sd, g.fu, &dp);
+    }
+    if (rc == SFMX_OK) rc = sfmx_sdist_query(ctx, g.sd, gq.data(), (int)d2.size(), 0, d2.data(), nullptr);
+    if (rc != SFMX_OK) {
+      const int keep = res->n_views;
+      sfmx_host_fusion_free_ex(res);
+      res->n_views = keep;
+      *ev = sfmx_surface_eval_result{};
+      return rc;
+    }
+    eval_side(d2, nullptr, gt->params, &ev->n_gt, &ev->comp_within, nullptr, nullptr, nullptr);
+    eval_finish(ev);
   }
   if (ply_path) {
     if (nf == 0) {

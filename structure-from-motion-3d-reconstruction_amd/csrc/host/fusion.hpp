@@ -64,4 +64,38 @@ int sfmx_host_fusion_mesh_cl(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
                              int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, sfmx_fusion_result_ex* res,
                              const char* ply_path, char* warn, int warn_cap);
+
+// Surface accuracy and completeness, host arithmetic on squared distances from the device (sfmx_sdist_*).  Both
+// sample at the vertices a face uses.  Accuracy: dist = sqrt(d2) from each reconstruction vertex to the ground-truth mesh, a
+// clipped distance counting as d_max; accuracy = sorted(dist)[ceil(percentile / 100 n) - 1] (nearest rank), acc_within = the
+// count with dist <= tau, acc_mean = one sequential sum in index order / n, acc_max.  Completeness: comp_within = the count of
+// ground-truth vertices with dist <= tau to the reconstruction, completeness = comp_within / n_gt.  With no vertices on a side
+// its doubles are NaN.  d_max > 0 and 0 <= tau <= d_max have no defaults; 0 < percentile <= 100; cell as sfmx_sdist_params.
+struct sfmx_surface_eval_params {
+  double d_max, tau, percentile, cell;
+};
+struct sfmx_surface_eval_result {
+  double accuracy, acc_mean, acc_max, completeness;
+  int acc_within, n_rec, comp_within, n_gt;
+};
+// every array is a host pointer; SFMX_ERR_INVALID for a face index out of range or a non-finite used coordinate
+int sfmx_host_surface_eval(sfmx_ctx* ctx, const double* rec_verts, int n_rec_verts, const int32_t* rec_faces, int n_rec_faces,
+                           const double* gt_verts, int n_gt_verts, const int32_t* gt_faces, int n_gt_faces,
+                           const sfmx_surface_eval_params* p, sfmx_surface_eval_result* out);
+
+// sfmx_host_fusion_mesh_cl with the final mesh (the cleaned one when clean is given) evaluated against a ground-truth mesh on
+// the host; the final mesh is taken from the device where the last stage left it.  gt = NULL: exactly
+// sfmx_host_fusion_mesh_cl (ev is not touched).  A surface without faces has n_rec = 0.
+struct sfmx_surface_gt {
+  const double* verts;
+  int n_verts;
+  const int32_t* faces;
+  int n_faces;
+  sfmx_surface_eval_params params;
+};
+int sfmx_host_fusion_mesh_ev(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
 }

@@ -183,6 +183,54 @@ class FusionResultEx(ctypes.Structure):
 APPEARANCE_KEYS = ("depth_tol", "cull", "fill")
 CONSISTENCY_KEYS = ("rel_tol", "reproj_px", "min_support")
 CLEAN_KEYS = ("min_faces", "min_permille")
+EVALUATE_KEYS = ("gt_verts", "gt_faces", "d_max", "tau", "percentile", "cell")
+EVALUATION_FIELDS = ("accuracy", "acc_within", "acc_mean", "acc_max", "n_rec", "completeness", "comp_within", "n_gt")
+
+
+class SurfaceEvalParams(ctypes.Structure):
+    _fields_ = [("d_max", c_double), ("tau", c_double), ("percentile", c_double), ("cell", c_double)]
+
+
+class SurfaceEvalResult(ctypes.Structure):
+    _fields_ = [("accuracy", c_double), ("acc_mean", c_double), ("acc_max", c_double), ("completeness", c_double),
+                ("acc_within", c_int), ("n_rec", c_int), ("comp_within", c_int), ("n_gt", c_int)]
+
+    def asdict(self):
+        return {k: (float if k in ("accuracy", "acc_mean", "acc_max", "completeness") else int)(getattr(self, k)) for k in EVALUATION_FIELDS}
+
+
+class SurfaceGt(ctypes.Structure):
+    _fields_ = [("verts", POINTER(c_double)), ("n_verts", c_int), ("faces", POINTER(c_int)), ("n_faces", c_int),
+                ("params", SurfaceEvalParams)]
+
+
+def _eval_params(d_max, tau, percentile, cell) -> SurfaceEvalParams:
+    if d_max is None or tau is None:
+        raise TypeError("surface evaluation needs d_max and tau (lengths in the mesh's units; there is no default)")
+    if not float(tau) <= float(d_max):
+        raise ValueError(f"tau = {tau} must not exceed d_max = {d_max}")
+    return SurfaceEvalParams(float(d_max), float(tau), float(percentile), float(cell))
+
+
+def surface_eval(ctx: capi.Context, verts, faces, gt_verts, gt_faces, d_max=None, tau=None, percentile=90.0, cell=0.0) -> dict:
+    """Accuracy and completeness of the reconstruction (verts, faces) against the ground truth (gt_verts, gt_faces), sampled at
+    the vertices a face uses; the distances come from the device (capi.Sdist).  accuracy: the distance within
+    which `percentile` % of the reconstruction lies of the ground truth (nearest rank; distances are clipped at d_max);
+    acc_within / comp_within: vertices within tau; completeness = comp_within / n_gt.  d_max and tau are required, tau <= d_max.
+    Returns dict(accuracy, acc_within, acc_mean, acc_max, n_rec, completeness, comp_within, n_gt)."""
+    lib = load_host_library()
+    p = _eval_params(d_max, tau, percentile, cell)
+    rv = np.ascontiguousarray(verts, np.float64).reshape(-1, 3)
+    rf = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    gv = np.ascontiguousarray(gt_verts, np.float64).reshape(-1, 3)
+    gf = np.ascontiguousarray(gt_faces, np.int32).reshape(-1, 3)
+    out = SurfaceEvalResult()
+    dp, ip = POINTER(c_double), POINTER(c_int)
+    rc = lib.sfmx_host_surface_eval(ctx.h_, rv.ctypes.data_as(dp), c_int(len(rv)), rf.ctypes.data_as(ip), c_int(len(rf)),
+                                    gv.ctypes.data_as(dp), c_int(len(gv)), gf.ctypes.data_as(ip), c_int(len(gf)), byref(p), byref(out))
+    if rc != capi.SFMX_OK:
+        raise capi.SfmxError(rc, (ctx.lib.sfmx_last_error(ctx.h_) or b"").decode() or "surface_eval")
+    return out.asdict()
 
 
 def _split_fusion_params(params: dict):
@@ -194,7 +242,7 @@ def _split_fusion_params(params: dict):
 
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
-         consistency=False, clean=False, **params) -> dict:
+         consistency=False, clean=False, evaluate=None, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -209,7 +257,10 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     the unfiltered maps.
     clean: True, or dict(min_faces=, min_permille=) -- the small connected components of the extracted surface are removed on
     the device before the arrays and the PLY are made; with appearance the cleaned vertices are shaded.  The dict
-    gains clean = dict(components=, largest=, verts_removed=, faces_removed=)."""
+    gains clean = dict(components=, largest=, verts_removed=, faces_removed=).
+    evaluate: dict(gt_verts=, gt_faces=, d_max=, tau=, percentile=90, cell=0) -- the final mesh (the cleaned one with clean) is
+    evaluated against the ground-truth mesh from where it lies on the device: the dict gains evaluation =
+    surface_eval()'s dict.  d_max and tau are required."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -251,12 +302,30 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             raise TypeError(f"unknown clean parameters {sorted(unknown)}")
         lp = capi.clean_params(**lkw)
         lcounts = np.zeros(4, np.int32)
-    if ap is not None or cp is not None or lp is not None:
+    gt = None
+    if evaluate is not None:
+        ekw = dict(evaluate)
+        unknown = set(ekw) - set(EVALUATE_KEYS)
+        if unknown:
+            raise TypeError(f"unknown evaluate parameters {sorted(unknown)}")
+        if "gt_verts" not in ekw or "gt_faces" not in ekw:
+            raise TypeError("evaluate needs gt_verts and gt_faces")
+        gv = np.ascontiguousarray(ekw["gt_verts"], np.float64).reshape(-1, 3)
+        gf = np.ascontiguousarray(ekw["gt_faces"], np.int32).reshape(-1, 3)
+        gt = SurfaceGt(gv.ctypes.data_as(dp), len(gv), gf.ctypes.data_as(POINTER(c_int)), len(gf),
+                       _eval_params(ekw.get("d_max"), ekw.get("tau"), ekw.get("percentile", 90.0), ekw.get("cell", 0.0)))
+        ev = SurfaceEvalResult()
+    if ap is not None or cp is not None or lp is not None or gt is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if lp is not None:
+        if gt is not None:
+            rc = lib.sfmx_host_fusion_mesh_ev(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None, byref(gt), byref(ev), *tail)
+        elif lp is not None:
             rc = lib.sfmx_host_fusion_mesh_cl(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None, byref(lp),
                                               lcounts.ctypes.data_as(POINTER(c_int)), *tail)
@@ -282,6 +351,8 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             out["consistency"] = dict(valid=[int(v) for v in done[:, 0]], kept=[int(v) for v in done[:, 1]])
         if lp is not None:
             out["clean"] = dict(zip(("components", "largest", "verts_removed", "faces_removed"), (int(v) for v in lcounts)))
+        if gt is not None:
+            out["evaluation"] = ev.asdict()
         return out
     res = FusionResult()
     rc = lib.sfmx_host_fusion_mesh(ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp),
@@ -328,7 +399,8 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     the run, fuse() on the run's own keyframe frames and kf_poses: the result gains fused_mesh = fuse()'s dict, and out_dir
     gains templeRing_mesh_fused.ply; 'appearance' (True or a dict, as fuse) adds normals and vertex grey to both;
     'consistency' (True or a dict, as fuse) filters the pairs' disparity maps against each other first; 'clean' (True or a
-    dict, as fuse) removes the surface's small connected components.  The run itself, its log and every other output are unchanged.
+    dict, as fuse) removes the surface's small connected components; 'evaluate' (a dict, as fuse) evaluates the final mesh against
+    a ground-truth mesh.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -392,8 +464,9 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         appearance = fz.pop("appearance", False)
         consistency = fz.pop("consistency", False)
         clean = fz.pop("clean", False)
+        evaluate = fz.pop("evaluate", None)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
-                                 appearance=appearance, consistency=consistency, clean=clean, **fz)
+                                 appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, **fz)
     return out
 
 

@@ -40,6 +40,38 @@ def make_scene(n_blobs: int = 20000, seed: int = 7, shell_scale: float = 1.0, co
     return dict(pts=pts, normals=d, sigma=sigma, amp=amp)
 
 
+def shell_radius(d, shell_scale: float = 1.0):
+    """the smooth part of make_scene's radius in the unit directions d [n][3] (the scene adds a jitter of sigma 0.003 before
+    the clip)"""
+    return np.clip(0.085 + 0.012 * np.sin(7.0 * d[:, 0]) * np.cos(5.0 * d[:, 1]), 0.07, 0.10) * shell_scale
+
+
+def shell_mesh(level: int, shell_scale: float = 1.0):
+    """(verts f64 [10 * 4^level + 2][3], faces i32 [20 * 4^level][3]): an icosahedron subdivided `level` times, faces outward,
+    each vertex moved along its direction to shell_radius -- the ground-truth surface of make_scene's shell up to its jitter."""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1),
+         (-t, 0, -1), (-t, 0, 1)]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    v = [np.asarray(x, np.float64) / np.linalg.norm(x) for x in v]
+    for _ in range(level):
+        mid, nf = {}, []
+        for a, b, c in f:
+            m = []
+            for i, j in ((a, b), (b, c), (c, a)):
+                k = (min(i, j), max(i, j))
+                if k not in mid:
+                    w = v[i] + v[j]
+                    v.append(w / np.linalg.norm(w))
+                    mid[k] = len(v) - 1
+                m.append(mid[k])
+            nf += [(a, m[0], m[2]), (b, m[1], m[0]), (c, m[2], m[1]), (m[0], m[1], m[2])]
+        f = nf
+    d = np.asarray(v)
+    return d * shell_radius(d, shell_scale)[:, None], np.asarray(f, np.int32)
+
+
 def ring_pose(angle_deg: float, dist: float = 0.65):
     """World->camera (R, t) for a camera on the ring at ``angle_deg`` looking at the origin."""
     a = np.deg2rad(angle_deg)

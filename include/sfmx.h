@@ -241,7 +241,11 @@ uint64_t sfmx_debug_klt_slow_steps(const sfmx_ctx* ctx);
  * (v_mfma_f64_16x16x4_f64), then blocked triangular solves.  entry_ij [m][2] / entry_v [m]: the distinct entries of
  * the LOWER triangle of L (row >= column), already summed; g3, x3 [n][3].  A different factorisation than the
  * reference's elimination: agrees with solve_gauss on the dense system to ~1e-12 relative (tests: 1e-9), not bit for
- * bit.  SFMX_ERR_SINGULAR where a pivot is not > 1e-15 (a keyframe not connected to node 0: the reference throws). */
+ * bit.  SFMX_ERR_SINGULAR where a pivot is not > 1e-15: that catches exact singularity (a zero row, a component without
+ * node 0 whose entries are all small integers), a matrix that is not positive definite and non-finite entries.  It does
+ * NOT decide connectivity: the last pivot of a cut-off component that holds loop edges is zero only up to rounding and
+ * lands either side of the threshold, so the caller checks on the graph that every node reaches node 0 before it calls
+ * (posegraph_optimize_centers does).  NaN in g3 alone is not an error: it fills its column of x3. */
 int sfmx_posegraph_solve(sfmx_ctx* ctx, int n, const int32_t* entry_ij, const double* entry_v, int m,
                          const double* g3, double* x3);
 

@@ -18,8 +18,10 @@
 // elimination, fused multiply-adds in the matrix cores.  It agrees with solve_gauss on the dense system to ~1e-12
 // relative (tests hold it to 1e-9; graph Laplacians are far better conditioned in practice than their condition number
 // suggests), which is orders of magnitude inside the ATE tolerance of 1e-6.  The bit-exact dense path (ba.hip) stays the
-// default for the sizes the reference can run.  Singular systems (a keyframe not connected to node 0: the reference's
-// elimination meets a pivot < 1e-15 and throws) are reported as SFMX_ERR_SINGULAR.
+// default for the sizes the reference can run.  A pivot that is not > 1e-15 is reported as SFMX_ERR_SINGULAR: exact
+// singularity, a matrix that is not positive definite, non-finite entries.  Whether every keyframe is connected to node 0
+// is decided on the host before the call (posegraph_connected, pipeline.cpp): the last pivot of a cut-off component with
+// loop edges is zero only up to rounding, a few 1e-15 either side of the threshold.
 #include "sfmx_internal.h"
 
 #define PG_NB 32   // columns per factorisation step

@@ -1090,6 +1090,34 @@ static int posegraph_dense_max() {
   }
   return 6400;
 }
+// every node 0 ... n-1 reachable from node 0 over the off-diagonal entries (row, column) of entry_ij [m][2]?  Union-find with
+// path halving; diagonal entries (a self-edge leaves one) connect nothing.  The structured solve is positive definite exactly
+// then: the device's pivot test alone cannot tell, because the last pivot of a cut-off component that holds loop edges is 0 only
+// up to rounding (a few 1e-15 either side of the threshold).
+bool posegraph_connected(int n, const std::int32_t* entry_ij, int m) {
+  if (n < 1) return false;
+  std::vector<int> parent((size_t)n);
+  for (int i = 0; i < n; i++) parent[(size_t)i] = i;
+  auto find = [&](int a) {
+    while (parent[(size_t)a] != a) {
+      parent[(size_t)a] = parent[(size_t)parent[(size_t)a]];
+      a = parent[(size_t)a];
+    }
+    return a;
+  };
+  int components = n;
+  for (int e = 0; e < m; e++) {
+    const int a = entry_ij[2 * e], b = entry_ij[2 * e + 1];
+    if (a < 0 || b < 0 || a >= n || b >= n || a == b) continue;
+    const int ra = find(a), rb = find(b);
+    if (ra != rb) {
+      parent[(size_t)ra] = rb;
+      components--;
+    }
+  }
+  return components == 1;
+}
+
 bool posegraph_optimize_centers(sfmx_ctx* ctx, std::vector<Keyframe>& kfs, const std::vector<PGEdge>& edges) {
   const int N = (int)kfs.size();
   if (N < 2 || edges.empty()) return false;
@@ -1144,11 +1172,10 @@ bool posegraph_optimize_centers(sfmx_ctx* ctx, std::vector<Keyframe>& kfs, const
     rc = sfmx_solve_dense(ctx, H.data(), g.data(), D, dc.data());
   } else {
     if (ent_v.empty()) return false;
-    // a node no edge touches has an all-zero row: the reference's elimination meets a zero pivot there and gives up
-    std::vector<char> touched((size_t)N, 0);
-    for (size_t k = 0; k < ent_v.size(); k++) touched[(size_t)ent_ij[2 * k]] = touched[(size_t)ent_ij[2 * k + 1]] = 1;
-    for (int i = 0; i < N; i++)
-      if (!touched[(size_t)i]) return false;
+    // a keyframe with no path to node 0 makes L singular: the reference's elimination meets a pivot that is zero in exact
+    // arithmetic there and gives up.  Decided here, on the graph, before any device work: with loop edges inside the cut-off
+    // part that pivot is rounding noise, and neither the reference's threshold nor the device's decides it reliably.
+    if (!posegraph_connected(N, ent_ij.data(), (int)ent_v.size())) return false;
     rc = sfmx_posegraph_solve(ctx, N, ent_ij.data(), ent_v.data(), (int)ent_v.size(), g.data(), dc.data());
   }
   if (rc == SFMX_ERR_SINGULAR) return false;
@@ -2352,6 +2379,12 @@ int sfmx_host_posegraph(sfmx_ctx* ctx, int n_kf, const double* R9s, double* cent
   } catch (const std::exception&) {
     return -SFMX_ERR_INVALID;
   }
+}
+
+// the reachability check of the structured pose-graph branch on its own: 1 = every node reachable from node 0, 0 = not
+int sfmx_host_posegraph_connected(int n, const int* entry_ij, int m) {
+  if (n < 1 || m < 0 || (m > 0 && !entry_ij)) return -SFMX_ERR_INVALID;
+  return sfmx_host::posegraph_connected(n, entry_ij, m) ? 1 : 0;
 }
 
 // the CLI's file readers on their own (csrc/host/cli_io.hpp), for the surface tests against the reference's readers

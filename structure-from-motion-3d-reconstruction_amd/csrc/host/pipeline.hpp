@@ -477,6 +477,7 @@ class AsyncLane {
 };
 
 bool posegraph_optimize_centers(sfmx_ctx* ctx, std::vector<Keyframe>& kfs, const std::vector<PGEdge>& edges);
+bool posegraph_connected(int n, const std::int32_t* entry_ij, int m);
 
 // optional sparse-mesh export of the CLI (mesh.cpp; T:1226-1461): empty outputs = skipped
 void build_sparse_mesh(const Mat3& K, const Pose& kf_pose, const MapState& map, int img_w, int img_h, int max_points, int grid_px,

@@ -508,6 +508,54 @@ int sfmx_sdist_stats(const sfmx_sdist* sd, int* dims3, int* entries, double* cel
 /* device time (us) from the first to the last launch of the last sfmx_sdist_set_target* / _query* when timing is on, else 0 */
 double sfmx_sdist_last_us(const sfmx_sdist* sd);
 
+/* ---- rendering the volume from any camera: TSDF ray casting ------------------------------------------------ */
+/* Per pixel (x, y) of a pinhole camera the ray c + z dw, dw = R_rw^T ((x - cx) / f, (y - cy) / f, 1), is sampled at the depths
+ * z_k = z_min + k step, k = 0 .. K - 1 with K = floor((z_max - z_min) / step) + 1.  The value at a sample is the trilinear
+ * interpolation of s = sum / count over the 8 corners of its cell and exists only inside the grid with all 8 corners defined
+ * (count >= min_weight).  The hit is the first k >= 1 whose two samples both have a value with s_{k-1} > 0 >= s_k, placed by
+ * linear interpolation between them; its normal is the volume's gradient interpolated the same way at the hit
+ * point and normalised (0 where a corner of that cell is undefined or the gradient vanishes); shaded is a head light,
+ * round(255 max(0, -n . dw / |dw|)).  A pixel without a hit has depth 0, a zero point and normal, and shaded = background.
+ * Everything is IEEE double in one fixed expression order, the sample lattice never moves (samples outside the grid are
+ * skipped, which is exact), so every output is bit-identical to the NumPy restatement in tests/raycast_ref.py.
+ * The camera is a sfmx_fusion_view: R_rw, c_left, f (> 0), cx, cy, w, h are used, B is ignored.  w <= 4096, w * h <= 2^24. */
+#define SFMX_RAYCAST_MAX_SAMPLES (1 << 20) /* K */
+#define SFMX_RAYCAST_MAX_PIXELS (1 << 24)  /* w * h */
+typedef struct sfmx_raycast sfmx_raycast;  /* the device outputs of the last render; they grow on demand and are kept */
+typedef struct sfmx_raycast_params {
+  double z_min, z_max; /* depths along the optical axis: 0 < z_min < z_max, finite; no default */
+  double step;         /* sample spacing in depth, >= 0; 0 (default) = voxel / 2, resolved per call */
+  int min_weight;      /* a grid point is defined when count >= min_weight; 0 (default) = the volume's own */
+  uint8_t background;  /* shaded value of a pixel without a hit (default 0) */
+} sfmx_raycast_params;
+void sfmx_raycast_default_params(sfmx_raycast_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID (K is checked when step > 0; a step of 0 is checked again per render); needs no device */
+int sfmx_raycast_check_params(const sfmx_raycast_params* p);
+int sfmx_raycast_create(sfmx_ctx* ctx, sfmx_raycast** out);
+void sfmx_raycast_destroy(sfmx_ctx* ctx, sfmx_raycast* rc);
+/* integrates fu's pending views (as sfmx_fusion_extract does), then renders its volume.  A render that hits nothing is not an
+ * error.  A failed render leaves no result. */
+int sfmx_raycast_render(sfmx_ctx* ctx, sfmx_raycast* rc, sfmx_fusion* fu, const sfmx_fusion_view* view, const sfmx_raycast_params* p);
+/* the same for any volume: sum double / count int32 [nz][ny][nx], host pointers (copied) or (on_device = 1) device pointers
+ * (read in place); vol gives origin, voxel, nx, ny, nz and min_weight and is checked by sfmx_fusion_check_params */
+int sfmx_raycast_render_arrays(sfmx_ctx* ctx, sfmx_raycast* rc, const sfmx_fusion_params* vol, const double* sum, const int32_t* count,
+                               int on_device, const sfmx_fusion_view* view, const sfmx_raycast_params* p);
+/* the last render to the host: depth double [h][w], normals / points double [h][w][3], shaded u8 [h][w], *hits = hit pixels;
+ * any may be NULL.  SFMX_ERR_INVALID before a render. */
+int sfmx_raycast_read(sfmx_ctx* ctx, sfmx_raycast* rc, double* depth, double* normals, double* points, uint8_t* shaded, int32_t* hits);
+/* the points and normals of all w * h pixels of the last render on the device (for sfmx_shade_vertices with on_device = 1);
+ * *n = w * h.  SFMX_ERR_INVALID (and NULLs, 0) before a render; needs no context.  Valid until the next render on rc. */
+int sfmx_raycast_device_surface(const sfmx_raycast* rc, const double** points, const double** normals, int* n);
+/* a novel-view grey image: sfmx_shade_vertices over the last render's device points and normals (no host round trip), then
+ * every pixel without a hit gets the render's background and 0 views.  grey_out u8 [h][w], views_out int32 [h][w]; either may
+ * be NULL.  SFMX_ERR_INVALID before a render. */
+int sfmx_raycast_shade(sfmx_ctx* ctx, sfmx_raycast* rc, sfmx_shade* sh, const sfmx_shade_params* p, uint8_t* grey_out,
+                       int32_t* views_out);
+/* device time (us) of the kernel of the last render when timing is on (sfmx_set_timing), else 0 */
+double sfmx_raycast_last_us(const sfmx_raycast* rc);
+/* samples the last render evaluated (inside the grid, up to each ray's hit), counted on the device; 0 before a render */
+uint64_t sfmx_raycast_last_samples(const sfmx_raycast* rc);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

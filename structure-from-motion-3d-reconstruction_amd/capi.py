@@ -47,6 +47,9 @@ SYMBOLS = [
     "sfmx_sdist_default_params", "sfmx_sdist_check_params", "sfmx_sdist_create", "sfmx_sdist_destroy", "sfmx_sdist_set_target",
     "sfmx_sdist_set_target_fusion", "sfmx_sdist_set_target_clean", "sfmx_sdist_query", "sfmx_sdist_query_fusion",
     "sfmx_sdist_query_clean", "sfmx_sdist_stats", "sfmx_sdist_last_us",
+    "sfmx_raycast_default_params", "sfmx_raycast_check_params", "sfmx_raycast_create", "sfmx_raycast_destroy", "sfmx_raycast_render",
+    "sfmx_raycast_render_arrays", "sfmx_raycast_read", "sfmx_raycast_device_surface", "sfmx_raycast_shade", "sfmx_raycast_last_us",
+    "sfmx_raycast_last_samples",
 ]
 
 
@@ -231,6 +234,32 @@ def sdist_check_params(d_max, cell=0.0) -> bool:
     return load_library().sfmx_sdist_check_params(byref(sdist_params(d_max, cell))) == SFMX_OK
 
 
+class RaycastParams(ctypes.Structure):
+    _fields_ = [("z_min", c_double), ("z_max", c_double), ("step", c_double), ("min_weight", c_int), ("background", c_uint8)]
+
+
+RAYCAST_MAX_SAMPLES, RAYCAST_MAX_PIXELS = 1 << 20, 1 << 24  # SFMX_RAYCAST_MAX_SAMPLES / _PIXELS
+
+
+def raycast_params(z_min=0.0, z_max=0.0, step=0.0, min_weight=0, background=0) -> RaycastParams:
+    """z_min and z_max have no default (depths in the volume's units); step 0 = voxel / 2, min_weight 0 = the volume's own"""
+    if not 0 <= int(background) <= 255:
+        raise ValueError(f"background = {background} is not a byte")
+    return RaycastParams(float(z_min), float(z_max), float(step), int(min_weight), int(background))
+
+
+def raycast_default_params() -> dict:
+    """sfmx_raycast_default_params as a dict (needs no device)"""
+    p = RaycastParams()
+    load_library().sfmx_raycast_default_params(byref(p))
+    return dict(z_min=p.z_min, z_max=p.z_max, step=p.step, min_weight=p.min_weight, background=p.background)
+
+
+def raycast_check_params(**kw) -> bool:
+    """True if sfmx_raycast_render would accept the parameters (a step of 0 is checked again against the voxel); needs no device"""
+    return load_library().sfmx_raycast_check_params(byref(raycast_params(**kw))) == SFMX_OK
+
+
 def stereo_check_params(w: int, h: int, **kw) -> bool:
     """True if sfmx_stereo_create would accept (w, h, params); needs no device"""
     return load_library().sfmx_stereo_check_params(c_int(w), c_int(h), byref(stereo_params(**kw))) == SFMX_OK
@@ -264,6 +293,8 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_consist_last_us.restype = c_double
         _lib.sfmx_clean_last_us.restype = c_double
         _lib.sfmx_sdist_last_us.restype = c_double
+        _lib.sfmx_raycast_last_us.restype = c_double
+        _lib.sfmx_raycast_last_samples.restype = c_uint64
     return _lib
 
 
@@ -725,6 +756,92 @@ class Sdist:
             pass
 
 
+class Raycast:
+    """sfmx_raycast: depth, point, normal and head-light shade per pixel of a pinhole camera, ray cast from a TSDF volume
+    (DESIGN.md 18).  The device outputs grow on demand and are kept between renders."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.shape = None  # (h, w) of the last render
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_raycast_create(ctx.h_, byref(self.h_)))
+
+    def render(self, vol, cam: dict, z_min, z_max, step=0.0, min_weight=0, background=0, w=None, h=None, read=True):
+        """vol: a Fusion (its pending views are integrated first), or (sum, count, origin, voxel) with sum float64 / count int32
+        [nz][ny][nx] numpy arrays, or ints (device pointers) followed by dims: (sum, count, origin, voxel, (nx, ny, nz)).
+        cam: dict(R_rw, c_left, f, cx, cy, w, h) (B is not used; w= / h= override the dict's image size).  Returns dict(depth f64 [h][w], normals / points
+        f64 [h][w][3], shaded u8 [h][w], hits), or None with read=False (the result stays on the device for read() / shade())."""
+        self.shape = None
+        p = raycast_params(z_min, z_max, step, min_weight, background)
+        w, h = int(cam["w"] if w is None else w), int(cam["h"] if h is None else h)
+        v = fusion_view({**cam, "B": cam.get("B", 0.0)}, w, h)
+        if isinstance(vol, Fusion):
+            self.ctx._chk(self.ctx.lib.sfmx_raycast_render(self.ctx.h_, self.h_, vol.h_, byref(v), byref(p)))
+        else:
+            sum_, count, origin, voxel = vol[:4]
+            on_dev = isinstance(sum_, int)
+            if on_dev != isinstance(count, int):
+                raise TypeError("sum and count: both host arrays or both device pointers")
+            if on_dev:
+                dims = vol[4]
+                ps, pc = c_void_p(sum_), c_void_p(count)
+            else:
+                sum_ = _f64(sum_)
+                count = np.ascontiguousarray(count, np.int32)
+                assert sum_.ndim == 3 and count.shape == sum_.shape
+                dims = sum_.shape[::-1]
+                ps, pc = sum_.ctypes.data_as(c_void_p), count.ctypes.data_as(c_void_p)
+            fp = fusion_params(origin, voxel, dims)
+            self.ctx._chk(self.ctx.lib.sfmx_raycast_render_arrays(self.ctx.h_, self.h_, byref(fp), ps, pc, c_int(1 if on_dev else 0),
+                                                                  byref(v), byref(p)))
+        self.shape = (int(h), int(w))
+        return self.read() if read else None
+
+    def read(self) -> dict:
+        """the last render: dict(depth, normals, points, shaded, hits)"""
+        h, w = self.shape or (1, 1)
+        depth, normals, points = np.zeros((h, w)), np.zeros((h, w, 3)), np.zeros((h, w, 3))
+        shaded, hits = np.zeros((h, w), np.uint8), c_int32(0)
+        self.ctx._chk(self.ctx.lib.sfmx_raycast_read(self.ctx.h_, self.h_, _p(depth, c_double), _p(normals, c_double), _p(points, c_double),
+                                                     _p(shaded, c_uint8), byref(hits)))
+        return dict(depth=depth, normals=normals, points=points, shaded=shaded, hits=int(hits.value))
+
+    def device_surface(self):
+        """(n = w * h, device pointer of the points, of the normals) of the last render; raises before one"""
+        pts, nrm, n = c_void_p(), c_void_p(), c_int(0)
+        rc = self.ctx.lib.sfmx_raycast_device_surface(self.h_, byref(pts), byref(nrm), byref(n))
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_raycast_device_surface: no render")
+        return n.value, pts.value, nrm.value
+
+    def shade(self, sh: "Shade", depth_tol, **params):
+        """a novel-view grey image of the last render from sh's retained views: (grey u8 [h][w], views int32 [h][w]); pixels
+        without a hit get the render's background and 0 views.  params: SHADE_DEFAULTS keys."""
+        p = shade_params(depth_tol, **params)
+        h, w = self.shape or (1, 1)
+        grey, views = np.zeros((h, w), np.uint8), np.zeros((h, w), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_raycast_shade(self.ctx.h_, self.h_, sh.h_, byref(p), _p(grey, c_uint8), _p(views, c_int32)))
+        return grey, views
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_raycast_last_us(self.h_))
+
+    def last_samples(self) -> int:
+        """samples the last render evaluated (inside the grid, up to each ray's hit)"""
+        return int(self.ctx.lib.sfmx_raycast_last_samples(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_raycast_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Stereo:
     """Device buffers of sfmx_stereo for one (w, h, params); disparity() runs rectify -> census -> SGM -> select -> speckle."""
 
@@ -1064,6 +1181,9 @@ class Context:
 
     def sdist(self) -> "Sdist":
         return Sdist(self)
+
+    def raycast(self) -> "Raycast":
+        return Raycast(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "sfmx_internal.h"
+#include "sfmx_tsdf.h"
 
 namespace {
 
@@ -113,12 +114,6 @@ struct FuView {
   int w, h;
 };
 
-struct FuGrid {
-  double ox, oy, oz, vs;
-  int nx, ny, nz;
-  int minw;
-};
-
 __global__ __launch_bounds__(256) void k_fu_integrate(double* __restrict__ sum, int* __restrict__ cnt, FuGrid g,
                                                       const FuView* __restrict__ views, int nv, const int16_t* __restrict__ stack,
                                                       double trunc, double disp_min, int bx, int by) {
@@ -154,12 +149,6 @@ __global__ __launch_bounds__(256) void k_fu_integrate(double* __restrict__ sum, 
   }
   sum[L] = s;
   cnt[L] = c;
-}
-
-__device__ __forceinline__ bool fu_value(const double* __restrict__ sum, const int* __restrict__ cnt, size_t L, int minw, double& s) {
-  const int c = cnt[L];
-  s = sum[L] / (double)c;
-  return c >= minw;
 }
 
 // inside bits of a cell's 8 corners (bit b = corner b inside), or -1 if the cell is not meshed
@@ -287,24 +276,6 @@ __global__ __launch_bounds__(256) void k_fu_emit_verts(const double* __restrict_
 }
 
 // ---- vertex normals: the gradient of s ------------------------------------------------------------------------
-// one axis of the gradient at a defined grid point with value s: central where both neighbours are defined, one-sided where
-// one is, 0 where neither (a neighbour outside the grid is undefined)
-__device__ __forceinline__ double fu_grad_axis(const double* __restrict__ sum, const int* __restrict__ cnt, int minw, double s, size_t L,
-                                               size_t stride, bool in_p, bool in_m) {
-  double sp = 0.0, sm = 0.0;
-  const bool dp = in_p && fu_value(sum, cnt, L + stride, minw, sp);
-  const bool dm = in_m && fu_value(sum, cnt, L - stride, minw, sm);
-  return dp && dm ? (sp - sm) * 0.5 : dp ? sp - s : dm ? s - sm : 0.0;
-}
-
-__device__ __forceinline__ void fu_grad(const double* __restrict__ sum, const int* __restrict__ cnt, const FuGrid& g, int i, int j, int k,
-                                        size_t L, double s, double& G0, double& G1, double& G2) {
-  const size_t sy = (size_t)g.nx, sz = (size_t)g.nx * g.ny;
-  G0 = fu_grad_axis(sum, cnt, g.minw, s, L, 1, i + 1 < g.nx, i > 0);
-  G1 = fu_grad_axis(sum, cnt, g.minw, s, L, sy, j + 1 < g.ny, j > 0);
-  G2 = fu_grad_axis(sum, cnt, g.minw, s, L, sz, k + 1 < g.nz, k > 0);
-}
-
 __global__ __launch_bounds__(256) void k_fu_emit_normals(const double* __restrict__ sum, const int* __restrict__ cnt, FuGrid g, int n,
                                                          const unsigned* __restrict__ vmask, const int* __restrict__ voff,
                                                          double* __restrict__ normals) {
@@ -706,4 +677,12 @@ int sfmx_fusion_device_mesh(const sfmx_fusion* fu, const double** verts, const d
   *faces = fu->out_f.as<int32_t>();
   *n_faces = fu->cur_f;
   return fu->cur_v;
+}
+
+int sfmx_fusion_device_volume(const sfmx_fusion* fu, const double** sum, const int32_t** count, sfmx_fusion_params* p) {
+  if (!fu->pending.empty()) return -1;
+  *sum = fu->sum;
+  *count = fu->cnt;
+  *p = fu->p;
+  return fu->n;
 }

@@ -152,6 +152,9 @@ int sfmx_fusion_device_surface(const sfmx_fusion* fu, const double** verts, cons
 // normals double [n][3] or NULL when that extraction made none); returns n, or -1 when there is none (never extracted, or the
 // volume has changed since)
 int sfmx_fusion_device_mesh(const sfmx_fusion* fu, const double** verts, const double** normals, const int32_t** faces, int* n_faces);
+// fusion.hip: the integrated volume on the device (sum double / count int32 [nz][ny][nx]) and the parameters it was created
+// with; returns the number of grid points, or -1 while views are pending (integrate first)
+int sfmx_fusion_device_volume(const sfmx_fusion* fu, const double** sum, const int32_t** count, sfmx_fusion_params* p);
 // clean.hip: the cleaned mesh of the last successful run on the device (verts double [n'][3], faces int32 [*n_faces][3]);
 // returns n', or -1 before a successful run
 int sfmx_clean_device_mesh(const sfmx_clean* cl, const double** verts, const int32_t** faces, int* n_faces);

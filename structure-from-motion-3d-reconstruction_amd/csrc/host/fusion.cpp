@@ -58,6 +58,12 @@
 #pragma weak sfmx_sdist_query
 #pragma weak sfmx_sdist_query_fusion
 #pragma weak sfmx_sdist_query_clean
+#pragma weak sfmx_raycast_check_params
+#pragma weak sfmx_raycast_create
+#pragma weak sfmx_raycast_destroy
+#pragma weak sfmx_raycast_render
+#pragma weak sfmx_raycast_read
+#pragma weak sfmx_raycast_shade
 
 namespace {
 
@@ -69,7 +75,9 @@ struct Guard {
   sfmx_consist* cs = nullptr;
   sfmx_clean* cl = nullptr;
   sfmx_sdist* sd = nullptr;
+  sfmx_raycast* rc = nullptr;
   ~Guard() {
+    if (rc) sfmx_raycast_destroy(ctx, rc);
     if (sd) sfmx_sdist_destroy(ctx, sd);
     if (cl) sfmx_clean_destroy(ctx, cl);
     if (cs) sfmx_consist_destroy(ctx, cs);
@@ -267,6 +275,16 @@ int sfmx_host_fusion_mesh_ev(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
                              int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
                              sfmx_surface_eval_result* ev, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_rc(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts, gt,
+                                  ev, nullptr, res, ply_path, warn, warn_cap);
+}
+
+int sfmx_host_fusion_mesh_rc(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, sfmx_fusion_result_ex* res,
+                             const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -277,6 +295,9 @@ int sfmx_host_fusion_mesh_ev(sfmx_ctx* ctx, const uint8_t* const* images, int on
   if (clean && (!&sfmx_clean_create || !&sfmx_clean_fusion || !&sfmx_clean_read || !&sfmx_clean_device_surface || !&sfmx_shade_vertices))
     return SFMX_ERR_UNSUPPORTED;
   if (gt && !sdist_linked()) return SFMX_ERR_UNSUPPORTED;
+  if (render && (!&sfmx_raycast_check_params || !&sfmx_raycast_create || !&sfmx_raycast_destroy || !&sfmx_raycast_render ||
+                 !&sfmx_raycast_read || !&sfmx_raycast_shade))
+    return SFMX_ERR_UNSUPPORTED;
   int rc = sfmx_stereo_check_params(w, h, sp);
   if (rc != SFMX_OK) return rc;
   rc = sfmx_fusion_check_params(fp);
@@ -307,6 +328,12 @@ int sfmx_host_fusion_mesh_ev(sfmx_ctx* ctx, const uint8_t* const* images, int on
     if (rc != SFMX_OK) return rc;
     if (clean_counts)
       for (int q = 0; q < 4; q++) clean_counts[q] = 0;
+  }
+  if (render) {
+    if (render->n_cameras < 0 || (render->n_cameras > 0 && (!render->cameras || !render->out))) return SFMX_ERR_INVALID;
+    rc = sfmx_raycast_check_params(&render->params);
+    if (rc != SFMX_OK) return rc;
+    for (int q = 0; q < render->n_cameras; q++) render->out[q].hits = 0;
   }
   std::string log;
   Guard g{ctx};
@@ -476,6 +503,23 @@ int sfmx_host_fusion_mesh_ev(sfmx_ctx* ctx, const uint8_t* const* images, int on
     }
     eval_side(d2, nullptr, gt->params, &ev->n_gt, &ev->comp_within, nullptr, nullptr, nullptr);
     eval_finish(ev);
+  }
+  if (render && render->n_cameras > 0) {
+    // the volume is untouched by the stages above; a failed render frees the mesh like any other failure
+    rc = sfmx_raycast_create(ctx, &g.rc);
+    for (int q = 0; rc == SFMX_OK && q < render->n_cameras; q++) {
+      sfmx_render_out& o = render->out[q];
+      rc = sfmx_raycast_render(ctx, g.rc, g.fu, &render->cameras[q], &render->params);
+      if (rc == SFMX_OK) rc = sfmx_raycast_read(ctx, g.rc, o.depth, o.normals, o.points, o.shaded, &o.hits);
+      if (rc == SFMX_OK && app && (o.grey || o.views)) rc = sfmx_raycast_shade(ctx, g.rc, g.sh, &ap, o.grey, o.views);
+    }
+    if (rc != SFMX_OK) {
+      const int keep = res->n_views;
+      sfmx_host_fusion_free_ex(res);
+      res->n_views = keep;
+      if (gt) *ev = sfmx_surface_eval_result{};
+      return rc;
+    }
   }
   if (ply_path) {
     if (nf == 0) {

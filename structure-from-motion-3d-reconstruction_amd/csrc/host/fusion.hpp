@@ -98,4 +98,33 @@ int sfmx_host_fusion_mesh_ev(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
                              int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
                              sfmx_surface_eval_result* ev, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_ev with the integrated volume rendered from further cameras by ray casting.  render =
+// NULL: exactly sfmx_host_fusion_mesh_ev.  Otherwise each camera (R_rw, c_left, f, cx, cy, w, h of a sfmx_fusion_view; B is not
+// used) is rendered with params after the surface has been made, and the arrays of out[i] that are not NULL are filled (caller
+// allocated: depth double [h][w], normals / points double [h][w][3], shaded u8 [h][w]).  With app, grey u8 [h][w] and views
+// int32 [h][w] are the shade stage over the render's device points and normals from the retained (unfiltered) shade views,
+// pixels without a hit getting params.background and 0; without app they are left alone.  The mesh, the PLY and every other
+// output are what they are without render.
+struct sfmx_render_out {
+  double* depth;
+  double* normals;
+  double* points;
+  uint8_t* shaded;
+  uint8_t* grey;
+  int32_t* views;
+  int32_t hits;
+};
+struct sfmx_render_request {
+  const sfmx_fusion_view* cameras;
+  int n_cameras;
+  sfmx_raycast_params params;
+  sfmx_render_out* out;  // [n_cameras]
+};
+int sfmx_host_fusion_mesh_rc(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, sfmx_fusion_result_ex* res,
+                             const char* ply_path, char* warn, int warn_cap);
 }

@@ -199,6 +199,27 @@ class SurfaceEvalResult(ctypes.Structure):
         return {k: (float if k in ("accuracy", "acc_mean", "acc_max", "completeness") else int)(getattr(self, k)) for k in EVALUATION_FIELDS}
 
 
+RENDER_KEYS = ("cameras", "w", "h", "z_min", "z_max", "step", "min_weight", "background", "pgm_prefix")
+
+
+class RenderOut(ctypes.Structure):
+    _fields_ = [("depth", POINTER(c_double)), ("normals", POINTER(c_double)), ("points", POINTER(c_double)), ("shaded", POINTER(c_ubyte)),
+                ("grey", POINTER(c_ubyte)), ("views", POINTER(c_int)), ("hits", c_int)]
+
+
+class RenderRequest(ctypes.Structure):
+    _fields_ = [("cameras", POINTER(capi.FusionView)), ("n_cameras", c_int), ("params", capi.RaycastParams), ("out", POINTER(RenderOut))]
+
+
+def write_pgm(path: str, image) -> None:
+    """a u8 [h][w] image as a binary PGM (P5)"""
+    image = np.ascontiguousarray(image, np.uint8)
+    h, w = image.shape
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (w, h))
+        f.write(image.tobytes())
+
+
 class SurfaceGt(ctypes.Structure):
     _fields_ = [("verts", POINTER(c_double)), ("n_verts", c_int), ("faces", POINTER(c_int)), ("n_faces", c_int),
                 ("params", SurfaceEvalParams)]
@@ -242,7 +263,7 @@ def _split_fusion_params(params: dict):
 
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
-         consistency=False, clean=False, evaluate=None, **params) -> dict:
+         consistency=False, clean=False, evaluate=None, render=None, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -260,7 +281,12 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     gains clean = dict(components=, largest=, verts_removed=, faces_removed=).
     evaluate: dict(gt_verts=, gt_faces=, d_max=, tau=, percentile=90, cell=0) -- the final mesh (the cleaned one with clean) is
     evaluated against the ground-truth mesh from where it lies on the device: the dict gains evaluation =
-    surface_eval()'s dict.  d_max and tau are required."""
+    surface_eval()'s dict.  d_max and tau are required.
+    render: dict(cameras=[dict(R_rw, c_left, f, cx, cy), ...], w=, h=, z_min=, z_max=, step=0, min_weight=0, background=0,
+    pgm_prefix=None) -- the integrated volume is ray cast from each camera at w x h (z_min and z_max are required):
+    the dict gains renders = [dict(depth, normals, points, shaded, hits), ...]; with appearance each also carries grey and
+    pixel_views, the shade stage over the render's points and normals from the retained views.  pgm_prefix writes
+    <prefix>_<i>_shaded.pgm (and _grey.pgm with appearance).  The mesh and the PLY are what they are without render."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -315,12 +341,44 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         gt = SurfaceGt(gv.ctypes.data_as(dp), len(gv), gf.ctypes.data_as(POINTER(c_int)), len(gf),
                        _eval_params(ekw.get("d_max"), ekw.get("tau"), ekw.get("percentile", 90.0), ekw.get("cell", 0.0)))
         ev = SurfaceEvalResult()
-    if ap is not None or cp is not None or lp is not None or gt is not None:
+    rq = None
+    if render is not None:
+        rkw = dict(render)
+        unknown = set(rkw) - set(RENDER_KEYS)
+        if unknown:
+            raise TypeError(f"unknown render parameters {sorted(unknown)}")
+        missing = [k for k in ("cameras", "w", "h", "z_min", "z_max") if k not in rkw]
+        if missing:
+            raise TypeError(f"render needs {missing}")
+        rw, rh = int(rkw["w"]), int(rkw["h"])
+        if rw < 1 or rh < 1 or rw > 4096 or rw * rh > capi.RAYCAST_MAX_PIXELS:
+            raise ValueError(f"render size {rw} x {rh} is outside 1 <= w <= 4096, w * h <= 2^24")
+        rcams = list(rkw["cameras"])
+        rviews = (capi.FusionView * max(len(rcams), 1))(*[capi.fusion_view({**c, "B": c.get("B", 0.0)}, rw, rh) for c in rcams])
+        rarr = [dict(depth=np.zeros((rh, rw)), normals=np.zeros((rh, rw, 3)), points=np.zeros((rh, rw, 3)), shaded=np.zeros((rh, rw), np.uint8))
+                for _ in rcams]
+        if ap is not None:
+            for a in rarr:
+                a.update(grey=np.zeros((rh, rw), np.uint8), pixel_views=np.zeros((rh, rw), np.int32))
+        ub, ip = POINTER(c_ubyte), POINTER(c_int)
+        routs = (RenderOut * max(len(rcams), 1))(*[
+            RenderOut(a["depth"].ctypes.data_as(dp), a["normals"].ctypes.data_as(dp), a["points"].ctypes.data_as(dp), a["shaded"].ctypes.data_as(ub),
+                      a["grey"].ctypes.data_as(ub) if ap is not None else None, a["pixel_views"].ctypes.data_as(ip) if ap is not None else None, 0)
+            for a in rarr])
+        rq = RenderRequest(rviews, len(rcams), capi.raycast_params(rkw["z_min"], rkw["z_max"], rkw.get("step", 0.0), rkw.get("min_weight", 0),
+                                                                   rkw.get("background", 0)), routs)
+    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if gt is not None:
+        if rq is not None:
+            rc = lib.sfmx_host_fusion_mesh_rc(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None, byref(rq), *tail)
+        elif gt is not None:
             rc = lib.sfmx_host_fusion_mesh_ev(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -353,6 +411,13 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             out["clean"] = dict(zip(("components", "largest", "verts_removed", "faces_removed"), (int(v) for v in lcounts)))
         if gt is not None:
             out["evaluation"] = ev.asdict()
+        if rq is not None:
+            out["renders"] = [dict(a, hits=int(routs[i].hits)) for i, a in enumerate(rarr)]
+            if rkw.get("pgm_prefix"):
+                for i, a in enumerate(rarr):
+                    write_pgm(f"{rkw['pgm_prefix']}_{i}_shaded.pgm", a["shaded"])
+                    if ap is not None:
+                        write_pgm(f"{rkw['pgm_prefix']}_{i}_grey.pgm", a["grey"])
         return out
     res = FusionResult()
     rc = lib.sfmx_host_fusion_mesh(ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp),
@@ -400,7 +465,7 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     gains templeRing_mesh_fused.ply; 'appearance' (True or a dict, as fuse) adds normals and vertex grey to both;
     'consistency' (True or a dict, as fuse) filters the pairs' disparity maps against each other first; 'clean' (True or a
     dict, as fuse) removes the surface's small connected components; 'evaluate' (a dict, as fuse) evaluates the final mesh against
-    a ground-truth mesh.  The run itself, its log and every other output are unchanged.
+    a ground-truth mesh; 'render' (a dict, as fuse) ray casts the volume from further cameras.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -465,8 +530,9 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         consistency = fz.pop("consistency", False)
         clean = fz.pop("clean", False)
         evaluate = fz.pop("evaluate", None)
+        render = fz.pop("render", None)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
-                                 appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, **fz)
+                                 appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, **fz)
     return out
 
 

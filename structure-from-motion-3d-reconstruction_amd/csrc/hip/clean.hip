@@ -16,8 +16,8 @@
 //   k_cl_stats       per vertex: vcf[v] = cf[lab[v]]; per root with cf > 0 a wave-reduced atomicMax into `largest` and a
 //                    ballot / popcount add into `n_components`
 //   k_cl_mark        per face: the keep rule on cf[lab[v0]]; a kept face flags its three corners
-//   k_cl_scan_*      exclusive int32 scans of the face flags and the vertex flags, one launch per level (fusion.hip's scheme:
-//                    no hand-off between workgroups inside a launch)
+//   k_scan_*         exclusive int32 scans of the face flags and the vertex flags, one launch per level (scan.hip: no
+//                    hand-off between workgroups inside a launch)
 //   k_cl_emit_verts  per kept vertex: its 24 bytes (and its normal's), its input index
 //   k_cl_emit_faces  per kept face: its renumbered indices, its input index
 // No kernel waits on another workgroup or spins on a memory word.  A face with an index out of range is skipped by every
@@ -144,48 +144,6 @@ __global__ __launch_bounds__(256) void k_cl_mark(const int* __restrict__ faces, 
   }
 }
 
-// exclusive scan of one 1024-element chunk per block (4 per thread).  in may equal out (every element is read before its
-// block writes).
-__global__ __launch_bounds__(256) void k_cl_scan_local(const int* in, int n, int* out, int* __restrict__ bsum) {
-  __shared__ int wsum[4];
-  const int base = blockIdx.x * 1024 + threadIdx.x * 4;
-  int v[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++) v[q] = base + q < n ? in[base + q] : 0;
-  const int tsum = v[0] + v[1] + v[2] + v[3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = tsum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int pre = incl - tsum;
-  for (int w = 0; w < wave; w++) pre += wsum[w];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    if (base + q < n) out[base + q] = pre;
-    pre += v[q];
-  }
-  if (threadIdx.x == 255) bsum[blockIdx.x] = pre;
-}
-
-__global__ __launch_bounds__(256) void k_cl_scan_add(int* out, int n, const int* __restrict__ offs) {
-  const int base = blockIdx.x * 1024 + threadIdx.x * 4;
-  const int o = offs[blockIdx.x];
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-    if (base + q < n) out[base + q] += o;
-}
-
-// counters[slot] = out[n - 1] + in[n - 1]
-__global__ void k_cl_scan_total(const int* __restrict__ in, const int* __restrict__ out, int n, int* __restrict__ counters, int slot) {
-  if (threadIdx.x != 0) return;
-  counters[slot] = out[n - 1] + in[n - 1];
-}
-
 __global__ __launch_bounds__(256) void k_cl_emit_verts(int n, const int* __restrict__ vkeep, const int* __restrict__ voff,
                                                        const unsigned long long* __restrict__ verts,
                                                        const unsigned long long* __restrict__ normals,
@@ -214,25 +172,6 @@ __global__ __launch_bounds__(256) void k_cl_emit_faces(const int* __restrict__ f
   fsrc[o] = f;
 }
 
-size_t cl_scan_aux(int n) {
-  size_t a = 0;
-  while (n > 1) {
-    n = (n + 1023) / 1024;
-    a += (size_t)n;
-  }
-  return a + 1;
-}
-
-// exclusive scan of in[0..n) into out, n >= 1; aux holds the block sums of every level
-void cl_scan(const int* in, int n, int* out, int* aux, hipStream_t s) {
-  const int nb = (n + 1023) / 1024;
-  k_cl_scan_local<<<nb, 256, 0, s>>>(in, n, out, aux);
-  if (nb > 1) {
-    cl_scan(aux, nb, aux, aux + nb, s);
-    k_cl_scan_add<<<nb, 256, 0, s>>>(out, n, aux);
-  }
-}
-
 }  // namespace
 
 struct sfmx_clean {
@@ -243,8 +182,7 @@ struct sfmx_clean {
   int *lab = nullptr, *vcf = nullptr;  // into work, of the last successful run
   bool done = false, has_normals = false;
   int n = 0, m = 0, nv_out = 0, nf_out = 0;
-  hipEvent_t ev[2] = {};
-  double last_us = 0.0;
+  StageTimer t;
 };
 
 namespace {
@@ -254,9 +192,9 @@ int cl_run(sfmx_ctx* ctx, sfmx_clean* cl, const double* verts, const double* nor
            const sfmx_clean_params* p, int* n_verts_out, int* n_faces_out, int* n_components, int* largest) {
   hipStream_t s = ctx->stream;
   cl->done = false;
-  cl->last_us = 0.0;
+  cl->t.us = 0.0;
   const size_t nn = (size_t)n, mm = (size_t)m;
-  const size_t aux = cl_scan_aux(n > m ? n : m);
+  const size_t aux = sfmx_scan_aux(n > m ? n : m);
   SFMX_HIP(ctx, cl->work.ensure((5 * nn + 2 * mm + aux + CL_COUNTERS) * 4));
   // the outputs are sized by the input: the kept counts are only known on the host after the launches
   SFMX_HIP(ctx, cl->out_v.ensure(nn * 24));
@@ -274,7 +212,7 @@ int cl_run(sfmx_ctx* ctx, sfmx_clean* cl, const double* verts, const double* nor
   int* ax = foff + mm;
   int* counters = ax + aux;
   const unsigned nbv = (unsigned)((nn + 255) / 256), nbf = (unsigned)((mm + 255) / 256);
-  if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(cl->ev[0], s));
+  SFMX_HIP(ctx, cl->t.begin(ctx));
   SFMX_HIP(ctx, hipMemsetAsync(counters, 0, CL_COUNTERS * 4, s));
   if (n > 0) k_cl_init<<<nbv, 256, 0, s>>>(n, lab, cf, vkeep);
   if (m > 0) k_cl_merge<<<nbf, 256, 0, s>>>(faces, m, n, lab, counters);
@@ -283,26 +221,23 @@ int cl_run(sfmx_ctx* ctx, sfmx_clean* cl, const double* verts, const double* nor
   if (n > 0) k_cl_stats<<<nbv, 256, 0, s>>>(n, lab, cf, vcf, counters);
   if (m > 0) {
     k_cl_mark<<<nbf, 256, 0, s>>>(faces, m, n, lab, cf, counters, p->min_faces, p->min_permille, fkeep, vkeep);
-    cl_scan(fkeep, m, foff, ax, s);
-    k_cl_scan_total<<<1, 64, 0, s>>>(fkeep, foff, m, counters, CL_NF_OUT);
+    sfmx_scan(fkeep, false, m, foff, ax, s);
+    sfmx_scan_total(fkeep, false, foff, m, counters + CL_NF_OUT, s);
   }
   if (n > 0) {
-    cl_scan(vkeep, n, voff, ax, s);
-    k_cl_scan_total<<<1, 64, 0, s>>>(vkeep, voff, n, counters, CL_NV_OUT);
+    sfmx_scan(vkeep, false, n, voff, ax, s);
+    sfmx_scan_total(vkeep, false, voff, n, counters + CL_NV_OUT, s);
     k_cl_emit_verts<<<nbv, 256, 0, s>>>(n, vkeep, voff, reinterpret_cast<const unsigned long long*>(verts),
                                         reinterpret_cast<const unsigned long long*>(normals), cl->out_v.as<unsigned long long>(),
                                         cl->out_n.as<unsigned long long>(), cl->vsrc.as<int>());
   }
   if (m > 0) k_cl_emit_faces<<<nbf, 256, 0, s>>>(faces, m, fkeep, foff, voff, cl->out_f.as<int>(), cl->fsrc.as<int>());
   SFMX_HIP(ctx, hipGetLastError());
-  if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(cl->ev[1], s));
+  SFMX_HIP(ctx, cl->t.end(ctx));
   int c[CL_COUNTERS] = {};
   SFMX_HIP(ctx, hipMemcpyAsync(c, counters, sizeof c, hipMemcpyDeviceToHost, s));
   SFMX_HIP(ctx, hipStreamSynchronize(s));
-  if (ctx->timing) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, cl->ev[0], cl->ev[1]) == hipSuccess) cl->last_us = (double)ms * 1000.0;
-  }
+  cl->t.collect(ctx);
   SFMX_REQUIRE(ctx, c[CL_FLAG] == 0);  // a face index outside [0, n)
   cl->lab = lab;
   cl->vcf = vcf;
@@ -346,8 +281,7 @@ int sfmx_clean_create(sfmx_ctx* ctx, sfmx_clean** out) {
   *out = nullptr;
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   auto* cl = new sfmx_clean;
-  hipError_t e = hipEventCreate(&cl->ev[0]);
-  if (e == hipSuccess) e = hipEventCreate(&cl->ev[1]);
+  const hipError_t e = cl->t.create();
   if (e != hipSuccess) {
     sfmx_clean_destroy(ctx, cl);
     return sfmx_fail(ctx, SFMX_ERR_HIP, "sfmx_clean_create", e);
@@ -363,8 +297,7 @@ void sfmx_clean_destroy(sfmx_ctx* ctx, sfmx_clean* cl) {
     (void)hipStreamSynchronize(ctx->stream);
   }
   for (DevBuf* b : {&cl->work, &cl->in_v, &cl->in_n, &cl->in_f, &cl->out_v, &cl->out_n, &cl->out_f, &cl->vsrc, &cl->fsrc}) b->release();
-  for (hipEvent_t ev : cl->ev)
-    if (ev) (void)hipEventDestroy(ev);
+  cl->t.destroy();
   delete cl;
 }
 
@@ -442,7 +375,7 @@ int sfmx_clean_device_surface(const sfmx_clean* cl, const double** verts, const 
   return cl->nv_out;
 }
 
-double sfmx_clean_last_us(const sfmx_clean* cl) { return cl ? cl->last_us : 0.0; }
+double sfmx_clean_last_us(const sfmx_clean* cl) { return cl ? cl->t.us : 0.0; }
 
 }  // extern "C"
 

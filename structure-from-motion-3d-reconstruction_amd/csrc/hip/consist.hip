@@ -2,7 +2,7 @@
 //
 // A sfmx_consist keeps, for every view added, the rectified left camera and its disparity map (int16) on the device.  The
 // filter lifts every valid pixel of every view to its 3-D point, projects it into every OTHER view with the integration's own
-// expressions (fusion.hip), and counts the views whose depth at that pixel agrees and whose own 3-D point
+// expressions (sfmx_view.h), and counts the views whose depth at that pixel agrees and whose own 3-D point
 // projects back onto the pixel.  A pixel with fewer than min_support such views becomes -16 in a second slab; the inputs are
 // never written, so the result does not depend on the schedule.
 //
@@ -19,13 +19,11 @@
 #include <cmath>
 
 #include "sfmx_internal.h"
+#include "sfmx_view.h"
 
 namespace {
 
-struct CsView {
-  double R[9], c[3], f, cx, cy, fB;
-  long long off;  // first pixel of the view in the three slabs
-  int w, h;
+struct CsView : DevView {  // off: first pixel of the view in the three slabs
   int first;  // the view's first block in the launch
   int bx;     // blocks per tile row: ceil(w / 64)
 };
@@ -48,8 +46,7 @@ __global__ __launch_bounds__(256) void k_cs_filter(const CsView* __restrict__ vi
   const bool in = x < V.w && y < V.h;
   const long long px = V.off + (long long)y * V.w + x;
   const int d = in ? (int)disp[px] : -16;
-  const double dd = (double)d / 16.0;
-  const bool valid = in && d != -16 && dd >= disp_min;
+  const bool valid = dv_disp_ok(d, disp_min);  // never a pixel outside the image: its d is the invalid mark
   const unsigned long long vmask = __ballot(valid);
   if (vmask == 0ull) {  // the whole wave (one row of 64 pixels)
     if (in) {
@@ -61,40 +58,26 @@ __global__ __launch_bounds__(256) void k_cs_filter(const CsView* __restrict__ vi
   int support = 0;
   if (valid) {
     const double xd = (double)x, yd = (double)y;
-    const double Z = V.fB / dd;
-    const double l0 = ((xd - V.cx) * Z) / V.f, l1 = ((yd - V.cy) * Z) / V.f;
-    const double X0 = V.c[0] + ((V.R[0] * l0 + V.R[3] * l1) + V.R[6] * Z);
-    const double X1 = V.c[1] + ((V.R[1] * l0 + V.R[4] * l1) + V.R[7] * Z);
-    const double X2 = V.c[2] + ((V.R[2] * l0 + V.R[5] * l1) + V.R[8] * Z);
+    double X0, X1, X2;
+    dv_lift(V, xd, yd, dv_disp_depth(V, d), X0, X1, X2);
     for (int j = 0; j < nv; j++) {
       if (j == i) continue;
-      const CsView& W = views[j];
-      const double p0 = X0 - W.c[0], p1 = X1 - W.c[1], p2 = X2 - W.c[2];
-      const double q2 = (W.R[6] * p0 + W.R[7] * p1) + W.R[8] * p2;
+      const DevView& W = views[j];
+      double p0, p1, p2, xr, yr;
+      const double q2 = dv_depth(W, X0, X1, X2, p0, p1, p2);
       if (!(q2 > 0.0)) continue;
-      const double q0 = (W.R[0] * p0 + W.R[1] * p1) + W.R[2] * p2;
-      const double q1 = (W.R[3] * p0 + W.R[4] * p1) + W.R[5] * p2;
-      const double u = (W.f * q0) / q2 + W.cx;
-      const double v = (W.f * q1) / q2 + W.cy;
-      const double xr = floor(u + 0.5), yr = floor(v + 0.5);
-      if (!(xr >= 0.0 && xr < (double)W.w && yr >= 0.0 && yr < (double)W.h)) continue;
-      const int d2 = disp[W.off + (long long)(int)yr * W.w + (int)xr];
-      const double dd2 = (double)d2 / 16.0;
-      if (d2 == -16 || !(dd2 >= disp_min)) continue;
-      const double Z2 = W.fB / dd2;
+      if (!dv_pixel(W, p0, p1, p2, q2, xr, yr)) continue;
+      const int d2 = disp[dv_index(W, xr, yr)];
+      if (!dv_disp_ok(d2, disp_min)) continue;
+      const double Z2 = dv_disp_depth(W, d2);
       if (!(fabs(Z2 - q2) <= rel_tol * q2)) continue;
       // the other view's own point, and where this view sees it
-      const double m0 = ((xr - W.cx) * Z2) / W.f, m1 = ((yr - W.cy) * Z2) / W.f;
-      const double Y0 = W.c[0] + ((W.R[0] * m0 + W.R[3] * m1) + W.R[6] * Z2);
-      const double Y1 = W.c[1] + ((W.R[1] * m0 + W.R[4] * m1) + W.R[7] * Z2);
-      const double Y2 = W.c[2] + ((W.R[2] * m0 + W.R[5] * m1) + W.R[8] * Z2);
-      const double s0 = Y0 - V.c[0], s1 = Y1 - V.c[1], s2 = Y2 - V.c[2];
-      const double t2 = (V.R[6] * s0 + V.R[7] * s1) + V.R[8] * s2;
+      double Y0, Y1, Y2, s0, s1, s2, ub, vb;
+      dv_lift(W, xr, yr, Z2, Y0, Y1, Y2);
+      const double t2 = dv_depth(V, Y0, Y1, Y2, s0, s1, s2);
       if (!(t2 > 0.0)) continue;
-      const double t0 = (V.R[0] * s0 + V.R[1] * s1) + V.R[2] * s2;
-      const double t1 = (V.R[3] * s0 + V.R[4] * s1) + V.R[5] * s2;
-      const double e0 = ((V.f * t0) / t2 + V.cx) - xd;
-      const double e1 = ((V.f * t1) / t2 + V.cy) - yd;
+      dv_project(V, s0, s1, s2, t2, ub, vb);
+      const double e0 = ub - xd, e1 = vb - yd;
       if (!((e0 * e0 + e1 * e1) <= reproj2)) continue;
       support += 1;
     }
@@ -122,44 +105,18 @@ struct sfmx_consist {
   DevBuf d_views, d_counts;
   std::vector<int32_t> counts;        // valid [n], kept [n] of the last filter
   bool filtered = false;
-  hipEvent_t ev[2] = {};
-  double last_us = 0.0;
+  StageTimer t;
 };
 
 namespace {
 
-bool cs_view_ok(const sfmx_fusion_view* v) {
-  if (!v || v->w <= 0 || v->h <= 0 || v->w > 4096 || (long long)v->w * v->h >= (1ll << 30)) return false;
-  for (double x : v->R_rw)
-    if (!std::isfinite(x)) return false;
-  for (double x : v->c_left)
-    if (!std::isfinite(x)) return false;
-  return std::isfinite(v->f) && std::isfinite(v->cx) && std::isfinite(v->cy) && std::isfinite(v->B);
-}
-
 int cs_add(sfmx_ctx* ctx, sfmx_consist* cs, const sfmx_fusion_view* v, const int16_t* disp16, hipMemcpyKind kind) {
   const long long px = (long long)v->w * v->h;
   SFMX_REQUIRE(ctx, cs->used + px < (1ll << 40));
-  const size_t used = (size_t)cs->used * 2, bytes = (size_t)(cs->used + px) * 2;
-  if (bytes > cs->disp.cap) {  // a grown slab gets the old contents (DevBuf parks the old block, so it is still there)
-    const void* old = cs->disp.p;
-    SFMX_HIP(ctx, cs->disp.ensure(bytes + bytes / 2));
-    if (old && used) SFMX_HIP(ctx, hipMemcpyAsync(cs->disp.p, old, used, hipMemcpyDeviceToDevice, ctx->stream));
-  }
+  SFMX_HIP(ctx, sfmx_grow_keep(cs->disp, (size_t)cs->used * 2, (size_t)(cs->used + px) * 2, ctx->stream));
   SFMX_HIP(ctx, hipMemcpyAsync(cs->disp.as<int16_t>() + cs->used, disp16, (size_t)px * 2, kind, ctx->stream));
   SFMX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller may reuse its buffer (a stereo object its map)
-  CsView cv{};
-  std::memcpy(cv.R, v->R_rw, sizeof cv.R);
-  std::memcpy(cv.c, v->c_left, sizeof cv.c);
-  cv.f = v->f;
-  cv.cx = v->cx;
-  cv.cy = v->cy;
-  cv.fB = v->f * v->B;
-  cv.off = cs->used;
-  cv.w = v->w;
-  cv.h = v->h;
-  cv.bx = (v->w + 63) / 64;
-  cs->views.push_back(cv);
+  cs->views.push_back(CsView{sfmx_dev_view(v, cs->used), 0, (v->w + 63) / 64});
   cs->src.push_back(*v);
   cs->used += px;
   cs->filtered = false;
@@ -192,8 +149,7 @@ int sfmx_consist_create(sfmx_ctx* ctx, sfmx_consist** out) {
   *out = nullptr;
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   auto* cs = new sfmx_consist;
-  hipError_t e = hipEventCreate(&cs->ev[0]);
-  if (e == hipSuccess) e = hipEventCreate(&cs->ev[1]);
+  const hipError_t e = cs->t.create();
   if (e != hipSuccess) {
     sfmx_consist_destroy(ctx, cs);
     return sfmx_fail(ctx, SFMX_ERR_HIP, "sfmx_consist_create", e);
@@ -209,8 +165,7 @@ void sfmx_consist_destroy(sfmx_ctx* ctx, sfmx_consist* cs) {
     (void)hipStreamSynchronize(ctx->stream);
   }
   for (DevBuf* b : {&cs->disp, &cs->out, &cs->sup, &cs->d_views, &cs->d_counts}) b->release();
-  for (hipEvent_t ev : cs->ev)
-    if (ev) (void)hipEventDestroy(ev);
+  cs->t.destroy();
   delete cs;
 }
 
@@ -221,18 +176,18 @@ int sfmx_consist_reset(sfmx_ctx* ctx, sfmx_consist* cs) {
   cs->counts.clear();
   cs->used = 0;
   cs->filtered = false;
-  cs->last_us = 0.0;
+  cs->t.us = 0.0;
   return SFMX_OK;
 }
 
 int sfmx_consist_add_view(sfmx_ctx* ctx, sfmx_consist* cs, const sfmx_fusion_view* view, const int16_t* disp16, int on_device) {
-  SFMX_REQUIRE(ctx, ctx && cs && disp16 && cs_view_ok(view));
+  SFMX_REQUIRE(ctx, ctx && cs && disp16 && sfmx_view_ok(view));
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   return cs_add(ctx, cs, view, disp16, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
 }
 
 int sfmx_consist_add_stereo_view(sfmx_ctx* ctx, sfmx_consist* cs, const sfmx_fusion_view* view, const sfmx_stereo* st) {
-  SFMX_REQUIRE(ctx, ctx && cs && st && cs_view_ok(view));
+  SFMX_REQUIRE(ctx, ctx && cs && st && sfmx_view_ok(view));
   int w = 0, h = 0;
   const int16_t* d16 = sfmx_stereo_device_disp16(st, &w, &h);
   SFMX_REQUIRE(ctx, view->w == w && view->h == h);
@@ -244,7 +199,7 @@ int sfmx_consist_view_count(const sfmx_consist* cs) { return cs ? (int)cs->views
 
 int sfmx_consist_filter(sfmx_ctx* ctx, sfmx_consist* cs, const sfmx_consist_params* p) {
   SFMX_REQUIRE(ctx, ctx && cs && sfmx_consist_check_params(p) == SFMX_OK);
-  cs->last_us = 0.0;
+  cs->t.us = 0.0;
   cs->filtered = false;
   const int nv = (int)cs->views.size();
   cs->counts.assign(2 * (size_t)nv, 0);
@@ -268,25 +223,22 @@ int sfmx_consist_filter(sfmx_ctx* ctx, sfmx_consist* cs, const sfmx_consist_para
   SFMX_HIP(ctx, cs->sup.ensure((size_t)cs->used));
   SFMX_HIP(ctx, hipMemcpyAsync(cs->d_views.p, cs->views.data(), sizeof(CsView) * (size_t)nv, hipMemcpyHostToDevice, s));
   SFMX_HIP(ctx, hipMemsetAsync(cs->d_counts.p, 0, 2 * (size_t)nv * 4, s));
-  if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(cs->ev[0], s));
+  SFMX_HIP(ctx, cs->t.begin(ctx));
   k_cs_filter<<<(unsigned)blocks, dim3(64, 4), 0, s>>>(cs->d_views.as<CsView>(), nv, cs->disp.as<int16_t>(), cs->out.as<int16_t>(),
                                                         cs->sup.as<uint8_t>(), cs->d_counts.as<int>(), p->rel_tol,
                                                         p->reproj_px * p->reproj_px, p->disp_min, p->min_support);
   SFMX_HIP(ctx, hipGetLastError());
-  if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(cs->ev[1], s));
+  SFMX_HIP(ctx, cs->t.end(ctx));
   SFMX_HIP(ctx, hipMemcpyAsync(cs->counts.data(), cs->d_counts.p, 2 * (size_t)nv * 4, hipMemcpyDeviceToHost, s));
   SFMX_HIP(ctx, hipStreamSynchronize(s));
-  if (ctx->timing) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, cs->ev[0], cs->ev[1]) == hipSuccess) cs->last_us = (double)ms * 1000.0;
-  }
+  cs->t.collect(ctx);
   cs->filtered = true;
   return SFMX_OK;
 }
 
 int sfmx_consist_read(sfmx_ctx* ctx, sfmx_consist* cs, int i, int16_t* disp16_out, uint8_t* support_out) {
   SFMX_REQUIRE(ctx, ctx && cs && cs->filtered && i >= 0 && i < (int)cs->views.size());
-  const CsView& v = cs->views[(size_t)i];
+  const DevView& v = cs->views[(size_t)i];
   const size_t px = (size_t)v.w * v.h;
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   if (disp16_out) SFMX_HIP(ctx, hipMemcpyAsync(disp16_out, cs->out.as<int16_t>() + v.off, px * 2, hipMemcpyDeviceToHost, ctx->stream));
@@ -303,7 +255,7 @@ int sfmx_consist_counts(sfmx_ctx* ctx, sfmx_consist* cs, int32_t* valid_out, int
   return SFMX_OK;
 }
 
-double sfmx_consist_last_us(const sfmx_consist* cs) { return cs ? cs->last_us : 0.0; }
+double sfmx_consist_last_us(const sfmx_consist* cs) { return cs ? cs->t.us : 0.0; }
 
 }  // extern "C"
 

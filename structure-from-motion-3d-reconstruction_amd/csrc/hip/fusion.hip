@@ -11,8 +11,7 @@
 //                      stay in registers across the pending views (read and written once per launch)
 //   k_fu_classify      one thread per cell: triangle count, and the edge slots its triangles use (atomicOr of 7-bit masks on
 //                      the edges' lower grid points)
-//   k_fu_scan_*        exclusive int32 scans over the triangle counts and the slot popcounts, one launch per level (no
-//                      inter-workgroup hand-off inside a launch)
+//   k_scan_*           exclusive int32 scans over the triangle counts and the slot popcounts (scan.hip)
 //   k_fu_emit_verts    one thread per grid point: its used slots, in slot order
 //   k_fu_emit_faces    one thread per cell: its triangles, in (tet, triangle) order
 //   k_fu_emit_normals  one thread per grid point, as k_fu_emit_verts: the volume's gradient at both ends of each used edge,
@@ -21,6 +20,7 @@
 
 #include "sfmx_internal.h"
 #include "sfmx_tsdf.h"
+#include "sfmx_view.h"
 
 namespace {
 
@@ -108,14 +108,8 @@ __constant__ const FuTable kFuTab = fu_make_table();
 __constant__ const int kFuChain1[6] = {1, 1, 2, 2, 4, 4};
 __constant__ const int kFuChain2[6] = {3, 5, 3, 6, 5, 6};
 
-struct FuView {
-  double R[9], c[3], f, cx, cy, fB;
-  long long off;  // first element of the view's map in the disparity stack
-  int w, h;
-};
-
 __global__ __launch_bounds__(256) void k_fu_integrate(double* __restrict__ sum, int* __restrict__ cnt, FuGrid g,
-                                                      const FuView* __restrict__ views, int nv, const int16_t* __restrict__ stack,
+                                                      const DevView* __restrict__ views, int nv, const int16_t* __restrict__ stack,
                                                       double trunc, double disp_min, int bx, int by) {
   int b = blockIdx.x;
   const int bi = b % bx;
@@ -129,20 +123,15 @@ __global__ __launch_bounds__(256) void k_fu_integrate(double* __restrict__ sum, 
   int c = cnt[L];
   const double ntrunc = -trunc;
   for (int n = 0; n < nv; n++) {
-    const FuView& V = views[n];
-    const double p0 = X0 - V.c[0], p1 = X1 - V.c[1], p2 = X2 - V.c[2];
-    const double q2 = (V.R[6] * p0 + V.R[7] * p1) + V.R[8] * p2;
+    const DevView& V = views[n];
+    double p0, p1, p2, x, y;
+    const double q2 = dv_depth(V, X0, X1, X2, p0, p1, p2);
     if (!(q2 > 0.0)) continue;
-    const double q0 = (V.R[0] * p0 + V.R[1] * p1) + V.R[2] * p2;
-    const double q1 = (V.R[3] * p0 + V.R[4] * p1) + V.R[5] * p2;
-    const double u = (V.f * q0) / q2 + V.cx;
-    const double v = (V.f * q1) / q2 + V.cy;
-    const double x = floor(u + 0.5), y = floor(v + 0.5);
-    if (!(x >= 0.0 && x < (double)V.w && y >= 0.0 && y < (double)V.h)) continue;
-    const int d = stack[V.off + (long long)(int)y * V.w + (int)x];
-    const double dd = (double)d / 16.0;
-    if (d == -16 || !(dd >= disp_min)) continue;
-    const double sdf = V.fB / dd - q2;
+    if (!dv_pixel(V, p0, p1, p2, q2, x, y)) continue;
+    const int d = stack[dv_index(V, x, y)];
+    if (!dv_disp_ok(d, disp_min)) continue;
+    const double Z = dv_disp_depth(V, d);
+    const double sdf = Z - q2;
     if (sdf < ntrunc) continue;
     s += sdf >= trunc ? 1.0 : sdf / trunc;
     c += 1;
@@ -198,53 +187,6 @@ __global__ __launch_bounds__(256) void k_fu_classify(const double* __restrict__ 
     }
   }
   tri_cnt[L] = nt;
-}
-
-// exclusive scan of one 1024-element chunk per block (4 per thread); popc = 1: scan popcount(in) instead of in.
-// in may equal out (every element is read before its block writes).
-__global__ __launch_bounds__(256) void k_fu_scan_local(const int* in, int popc, int n, int* out, int* __restrict__ bsum) {
-  __shared__ int wsum[4];
-  const int base = blockIdx.x * 1024 + threadIdx.x * 4;
-  int v[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const int x = base + q < n ? in[base + q] : 0;
-    v[q] = popc ? __popc((unsigned)x) : x;
-  }
-  const int tsum = v[0] + v[1] + v[2] + v[3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = tsum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int pre = incl - tsum;
-  for (int w = 0; w < wave; w++) pre += wsum[w];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    if (base + q < n) out[base + q] = pre;
-    pre += v[q];
-  }
-  if (threadIdx.x == 255) bsum[blockIdx.x] = pre;
-}
-
-__global__ __launch_bounds__(256) void k_fu_scan_add(int* out, int n, const int* __restrict__ offs) {
-  const int base = blockIdx.x * 1024 + threadIdx.x * 4;
-  const int o = offs[blockIdx.x];
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-    if (base + q < n) out[base + q] += o;
-}
-
-// totals[slot] = out[n - 1] + value(in[n - 1])
-__global__ void k_fu_scan_total(const int* __restrict__ in, int popc, const int* __restrict__ out, int n, int* __restrict__ totals,
-                                int slot) {
-  if (threadIdx.x != 0) return;
-  const int x = in[n - 1];
-  totals[slot] = out[n - 1] + (popc ? __popc((unsigned)x) : x);
 }
 
 __global__ __launch_bounds__(256) void k_fu_emit_verts(const double* __restrict__ sum, const int* __restrict__ cnt, FuGrid g, int n,
@@ -342,8 +284,8 @@ struct sfmx_fusion {
   int n = 0;  // grid points
   double* sum = nullptr;
   int* cnt = nullptr;
-  FuView* d_views = nullptr;
-  std::vector<FuView> pending;
+  DevView* d_views = nullptr;
+  std::vector<DevView> pending;
   DevBuf stack;            // int16 disparity maps of the pending views
   long long stack_used = 0;
   // extraction: triangle counts, face offsets, slot masks, vertex offsets (int32 [n] each), scan partials, totals
@@ -359,36 +301,8 @@ struct sfmx_fusion {
 
 namespace {
 
-size_t fu_scan_aux(int n) {
-  size_t a = 0;
-  while (n > 1) {
-    n = (n + 1023) / 1024;
-    a += (size_t)n;
-  }
-  return a + 1;
-}
-
-// exclusive scan of in[0..n) (or of its popcounts) into out; aux holds the block sums of every level
-void fu_scan(const int* in, int popc, int n, int* out, int* aux, hipStream_t s) {
-  const int nb = (n + 1023) / 1024;
-  k_fu_scan_local<<<nb, 256, 0, s>>>(in, popc, n, out, aux);
-  if (nb > 1) {
-    fu_scan(aux, 0, nb, aux, aux + nb, s);
-    k_fu_scan_add<<<nb, 256, 0, s>>>(out, n, aux);
-  }
-}
-
 FuGrid fu_grid(const sfmx_fusion* fu) {
   return FuGrid{fu->p.origin[0], fu->p.origin[1], fu->p.origin[2], fu->p.voxel, fu->p.nx, fu->p.ny, fu->p.nz, fu->p.min_weight};
-}
-
-bool fu_view_ok(const sfmx_fusion_view* v) {
-  if (!v || v->w <= 0 || v->h <= 0 || v->w > 4096 || (long long)v->w * v->h >= (1ll << 30)) return false;
-  for (double x : v->R_rw)
-    if (!std::isfinite(x)) return false;
-  for (double x : v->c_left)
-    if (!std::isfinite(x)) return false;
-  return std::isfinite(v->f) && std::isfinite(v->cx) && std::isfinite(v->cy) && std::isfinite(v->B);
 }
 
 int fu_timed(sfmx_ctx* ctx, sfmx_fusion* fu, int e0, int e1) {
@@ -418,17 +332,7 @@ int fu_queue(sfmx_ctx* ctx, sfmx_fusion* fu, const sfmx_fusion_view* v, const in
   const size_t bytes = (size_t)v->w * v->h * 2;
   SFMX_HIP(ctx, hipMemcpyAsync(fu->stack.as<int16_t>() + fu->stack_used, src, bytes, kind, ctx->stream));
   if (kind == hipMemcpyHostToDevice) SFMX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller may reuse its buffer
-  FuView fv{};
-  std::memcpy(fv.R, v->R_rw, sizeof fv.R);
-  std::memcpy(fv.c, v->c_left, sizeof fv.c);
-  fv.f = v->f;
-  fv.cx = v->cx;
-  fv.cy = v->cy;
-  fv.fB = v->f * v->B;
-  fv.off = fu->stack_used;
-  fv.w = v->w;
-  fv.h = v->h;
-  fu->pending.push_back(fv);
+  fu->pending.push_back(sfmx_dev_view(v, fu->stack_used));
   fu->stack_used += (long long)v->w * v->h;
   return SFMX_OK;
 }
@@ -471,7 +375,7 @@ int sfmx_fusion_create(sfmx_ctx* ctx, const sfmx_fusion_params* p, sfmx_fusion**
   const size_t n = (size_t)fu->n;
   hipError_t e = hipMalloc(&fu->sum, n * 8);
   if (e == hipSuccess) e = hipMalloc(&fu->cnt, n * 4);
-  if (e == hipSuccess) e = hipMalloc(&fu->d_views, sizeof(FuView) * (size_t)p->max_views);
+  if (e == hipSuccess) e = hipMalloc(&fu->d_views, sizeof(DevView) * (size_t)p->max_views);
   for (int q = 0; q < 6 && e == hipSuccess; q++) e = hipEventCreate(&fu->ev[q]);
   if (e == hipSuccess) e = hipMemsetAsync(fu->sum, 0, n * 8, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(fu->cnt, 0, n * 4, ctx->stream);
@@ -522,13 +426,13 @@ int sfmx_fusion_reset(sfmx_ctx* ctx, sfmx_fusion* fu) {
 }
 
 int sfmx_fusion_add_view(sfmx_ctx* ctx, sfmx_fusion* fu, const sfmx_fusion_view* view, const int16_t* disp16, int on_device) {
-  SFMX_REQUIRE(ctx, ctx && fu && disp16 && fu_view_ok(view));
+  SFMX_REQUIRE(ctx, ctx && fu && disp16 && sfmx_view_ok(view));
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   return fu_queue(ctx, fu, view, disp16, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
 }
 
 int sfmx_fusion_add_stereo_view(sfmx_ctx* ctx, sfmx_fusion* fu, const sfmx_fusion_view* view, const sfmx_stereo* st) {
-  SFMX_REQUIRE(ctx, ctx && fu && st && fu_view_ok(view));
+  SFMX_REQUIRE(ctx, ctx && fu && st && sfmx_view_ok(view));
   int w = 0, h = 0;
   const int16_t* d16 = sfmx_stereo_device_disp16(st, &w, &h);
   SFMX_REQUIRE(ctx, view->w == w && view->h == h);
@@ -554,7 +458,7 @@ int sfmx_fusion_integrate(sfmx_ctx* ctx, sfmx_fusion* fu) {
   const int nv = (int)fu->pending.size();
   fu->resident = -1;  // the volume changes: the surface kept on the device is no longer its surface
   fu->cur_v = fu->cur_f = -1;
-  SFMX_HIP(ctx, hipMemcpyAsync(fu->d_views, fu->pending.data(), sizeof(FuView) * (size_t)nv, hipMemcpyHostToDevice, s));
+  SFMX_HIP(ctx, hipMemcpyAsync(fu->d_views, fu->pending.data(), sizeof(DevView) * (size_t)nv, hipMemcpyHostToDevice, s));
   const FuGrid g = fu_grid(fu);
   const int bx = (g.nx + 63) / 64, by = (g.ny + 3) / 4;
   if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(fu->ev[0], s));
@@ -590,7 +494,7 @@ static int fu_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts_c
   fu->last_us = 0.0;
   hipStream_t s = ctx->stream;
   const int n = fu->n;
-  const size_t aux = fu_scan_aux(n);
+  const size_t aux = sfmx_scan_aux(n);
   SFMX_HIP(ctx, fu->ex.ensure(4 * (size_t)n * 4 + (aux + 2) * 4));
   int* tri = fu->ex.as<int>();
   int* foff = tri + n;
@@ -603,10 +507,10 @@ static int fu_extract(sfmx_ctx* ctx, sfmx_fusion* fu, double* verts, int verts_c
   if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(fu->ev[0], s));
   SFMX_HIP(ctx, hipMemsetAsync(vmask, 0, (size_t)n * 4, s));
   k_fu_classify<<<nb, 256, 0, s>>>(fu->sum, fu->cnt, g, n, tri, vmask);
-  fu_scan(tri, 0, n, foff, ax, s);
-  k_fu_scan_total<<<1, 64, 0, s>>>(tri, 0, foff, n, totals, 0);
-  fu_scan(reinterpret_cast<const int*>(vmask), 1, n, voff, ax, s);
-  k_fu_scan_total<<<1, 64, 0, s>>>(reinterpret_cast<const int*>(vmask), 1, voff, n, totals, 1);
+  sfmx_scan(tri, false, n, foff, ax, s);
+  sfmx_scan_total(tri, false, foff, n, totals, s);
+  sfmx_scan(reinterpret_cast<const int*>(vmask), true, n, voff, ax, s);
+  sfmx_scan_total(reinterpret_cast<const int*>(vmask), true, voff, n, totals + 1, s);
   SFMX_HIP(ctx, hipGetLastError());
   if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(fu->ev[1], s));
   int tot[2] = {0, 0};

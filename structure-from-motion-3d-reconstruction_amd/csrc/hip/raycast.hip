@@ -239,8 +239,7 @@ struct sfmx_raycast {
   int hits = 0;
   unsigned long long samples = 0;
   int background = 0;
-  hipEvent_t ev[2] = {};
-  double last_us = 0.0;
+  StageTimer t;
 };
 
 namespace {
@@ -263,7 +262,7 @@ int rc_samples(const sfmx_raycast_params* p, double step) {
 int rc_render(sfmx_ctx* ctx, sfmx_raycast* rc, const sfmx_fusion_params* vol, const double* d_sum, const int32_t* d_cnt,
               const sfmx_fusion_view* v, const sfmx_raycast_params* p) {
   rc->w = rc->h = 0;  // a failed render leaves no result
-  rc->last_us = 0.0;
+  rc->t.us = 0.0;
   const double step = p->step == 0.0 ? vol->voxel / 2.0 : p->step;
   SFMX_REQUIRE(ctx, step > 0.0);
   const int K = rc_samples(p, step);
@@ -289,12 +288,12 @@ int rc_render(sfmx_ctx* ctx, sfmx_raycast* rc, const sfmx_fusion_params* vol, co
   SFMX_HIP(ctx, hipMemsetAsync(rc->counters.p, 0, 16, s));
   unsigned long long* d_samples = rc->counters.as<unsigned long long>();
   int* d_hits = reinterpret_cast<int*>(d_samples + 1);
-  if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(rc->ev[0], s));
+  SFMX_HIP(ctx, rc->t.begin(ctx));
   k_rc_render<<<dim3((unsigned)((v->w + 15) / 16), (unsigned)((v->h + 15) / 16)), 256, 0, s>>>(
       d_sum, d_cnt, g, cam, m, rc->depth.as<double>(), rc->points.as<double>(), rc->normals.as<double>(), rc->shaded.as<uint8_t>(), d_hits,
       d_samples);
   SFMX_HIP(ctx, hipGetLastError());
-  if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(rc->ev[1], s));
+  SFMX_HIP(ctx, rc->t.end(ctx));
   unsigned long long back[2] = {0, 0};
   SFMX_HIP(ctx, hipMemcpyAsync(back, rc->counters.p, 16, hipMemcpyDeviceToHost, s));
   SFMX_HIP(ctx, hipStreamSynchronize(s));
@@ -303,10 +302,7 @@ int rc_render(sfmx_ctx* ctx, sfmx_raycast* rc, const sfmx_fusion_params* vol, co
   rc->background = (int)p->background;
   rc->w = v->w;
   rc->h = v->h;
-  if (ctx->timing) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, rc->ev[0], rc->ev[1]) == hipSuccess) rc->last_us = (double)ms * 1000.0;
-  }
+  rc->t.collect(ctx);
   return SFMX_OK;
 }
 
@@ -332,8 +328,7 @@ int sfmx_raycast_create(sfmx_ctx* ctx, sfmx_raycast** out) {
   *out = nullptr;
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   auto* rc = new sfmx_raycast;
-  hipError_t e = hipEventCreate(&rc->ev[0]);
-  if (e == hipSuccess) e = hipEventCreate(&rc->ev[1]);
+  const hipError_t e = rc->t.create();
   if (e != hipSuccess) {
     sfmx_raycast_destroy(ctx, rc);
     return sfmx_fail(ctx, SFMX_ERR_HIP, "sfmx_raycast_create", e);
@@ -349,8 +344,7 @@ void sfmx_raycast_destroy(sfmx_ctx* ctx, sfmx_raycast* rc) {
     (void)hipStreamSynchronize(ctx->stream);
   }
   for (DevBuf* b : {&rc->depth, &rc->normals, &rc->points, &rc->shaded, &rc->counters, &rc->in_sum, &rc->in_cnt}) b->release();
-  for (hipEvent_t ev : rc->ev)
-    if (ev) (void)hipEventDestroy(ev);
+  rc->t.destroy();
   delete rc;
 }
 
@@ -427,7 +421,7 @@ int sfmx_raycast_shade(sfmx_ctx* ctx, sfmx_raycast* rc, sfmx_shade* sh, const sf
   return SFMX_OK;
 }
 
-double sfmx_raycast_last_us(const sfmx_raycast* rc) { return rc ? rc->last_us : 0.0; }
+double sfmx_raycast_last_us(const sfmx_raycast* rc) { return rc ? rc->t.us : 0.0; }
 
 uint64_t sfmx_raycast_last_samples(const sfmx_raycast* rc) { return rc && rc->w > 0 ? rc->samples : 0; }
 

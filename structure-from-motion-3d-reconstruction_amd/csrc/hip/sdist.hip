@@ -14,8 +14,7 @@
 //                   anything is written, decides whether the cell size fits)
 //   k_sd_count      per face: atomicAdd(1) into each of those cells; blockIdx.y strides over a face's cells, so that a face
 //                   across the whole grid is not one thread's loop (the host sizes gridDim.y by the largest face)
-//   k_sd_scan_*     exclusive int32 scan, one launch per level (the scheme of fusion.hip and clean.hip: no hand-off between
-//                   workgroups inside a launch)
+//   k_scan_*        exclusive int32 scan, one launch per level (scan.hip: no hand-off between workgroups inside a launch)
 //   k_sd_fill       per face: its index into each cell's list, at offset + (atomicSub on the cell's count) - 1; the order inside
 //                   a list is arbitrary, the tie rule makes the result independent of it
 //   k_sd_qcell      per query: a non-finite coordinate sets the flag; a query outside the grid gets (dm2, -1) at once; the others
@@ -206,60 +205,6 @@ __global__ __launch_bounds__(256) void k_sd_fill(const double* __restrict__ V, c
     const int c = sd_cell(g, c0, wx, wy, j);
     const int slot = atomicSub(&ccnt[c], 1) - 1;
     ent[(size_t)coff[c] + (size_t)slot] = f;
-  }
-}
-
-// exclusive scan of one 1024-element chunk per block (4 per thread); in may equal out
-__global__ __launch_bounds__(256) void k_sd_scan_local(const int* in, int n, int* out, int* __restrict__ bsum) {
-  __shared__ int wsum[4];
-  const int base = blockIdx.x * 1024 + threadIdx.x * 4;
-  int v[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++) v[q] = base + q < n ? in[base + q] : 0;
-  const int tsum = v[0] + v[1] + v[2] + v[3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = tsum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int pre = incl - tsum;
-  for (int w = 0; w < wave; w++) pre += wsum[w];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    if (base + q < n) out[base + q] = pre;
-    pre += v[q];
-  }
-  if (threadIdx.x == 255) bsum[blockIdx.x] = pre;
-}
-
-__global__ __launch_bounds__(256) void k_sd_scan_add(int* out, int n, const int* __restrict__ offs) {
-  const int base = blockIdx.x * 1024 + threadIdx.x * 4;
-  const int o = offs[blockIdx.x];
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-    if (base + q < n) out[base + q] += o;
-}
-
-size_t sd_scan_aux(int n) {
-  size_t a = 0;
-  while (n > 1) {
-    n = (n + 1023) / 1024;
-    a += (size_t)n;
-  }
-  return a + 1;
-}
-
-// exclusive scan of in[0..n) into out, n >= 1; aux holds the block sums of every level
-void sd_scan(const int* in, int n, int* out, int* aux, hipStream_t s) {
-  const int nb = (n + 1023) / 1024;
-  k_sd_scan_local<<<nb, 256, 0, s>>>(in, n, out, aux);
-  if (nb > 1) {
-    sd_scan(aux, nb, aux, aux + nb, s);
-    k_sd_scan_add<<<nb, 256, 0, s>>>(out, n, aux);
   }
 }
 
@@ -495,7 +440,7 @@ int sd_set_target(sfmx_ctx* ctx, sfmx_sdist* sd, const double* verts, int nv, co
   const size_t nc1 = (size_t)ncells + 1;
   SFMX_HIP(ctx, sd->cells.ensure(2 * nc1 * 4));
   SFMX_HIP(ctx, sd->ent.ensure((size_t)c[SD_TOTAL] * 4));
-  SFMX_HIP(ctx, sd->aux.ensure(sd_scan_aux((int)nc1) * 4));
+  SFMX_HIP(ctx, sd->aux.ensure(sfmx_scan_aux((int)nc1) * 4));
   int* ccnt = sd->cells.as<int>();
   int* coff = ccnt + nc1;
   SFMX_HIP(ctx, hipMemsetAsync(ccnt, 0, nc1 * 4, s));
@@ -503,7 +448,7 @@ int sd_set_target(sfmx_ctx* ctx, sfmx_sdist* sd, const double* verts, int nv, co
   const unsigned long long want = (c[SD_LARGEST] + 63) / 64, room = (1ull << 24) / (unsigned long long)m;
   const unsigned slices = (unsigned)std::max(1ull, std::min(std::min(want, room), 65535ull));
   k_sd_count<<<dim3(nbf, slices), 256, 0, s>>>(V, F, m, g, ccnt);
-  sd_scan(ccnt, (int)nc1, coff, sd->aux.as<int>(), s);
+  sfmx_scan(ccnt, false, (int)nc1, coff, sd->aux.as<int>(), s);
   k_sd_fill<<<dim3(nbf, slices), 256, 0, s>>>(V, F, m, g, ccnt, coff, sd->ent.as<int>());
   SFMX_HIP(ctx, hipGetLastError());
   if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(sd->ev[1], s));
@@ -530,7 +475,7 @@ int sd_query(sfmx_ctx* ctx, sfmx_sdist* sd, const double* points, int n, double*
   SFMX_HIP(ctx, sd->out_f.ensure(nn * 4));
   SFMX_HIP(ctx, sd->qcells.ensure(4 * nc1 * 4));
   SFMX_HIP(ctx, sd->qwork.ensure(2 * nn * 4));
-  SFMX_HIP(ctx, sd->aux.ensure(sd_scan_aux((int)nc1) * 4));
+  SFMX_HIP(ctx, sd->aux.ensure(sfmx_scan_aux((int)nc1) * 4));
   int* qcnt = sd->qcells.as<int>();
   int* qoff = qcnt + nc1;
   int* icnt = qoff + nc1;
@@ -550,8 +495,8 @@ int sd_query(sfmx_ctx* ctx, sfmx_sdist* sd, const double* points, int n, double*
   unsigned long long c[SD_COUNTERS] = {};
   if (sd->has_grid) {
     k_sd_items<<<nbc, 256, 0, s>>>(qcnt, sd->ncells, icnt);
-    sd_scan(qcnt, (int)nc1, qoff, sd->aux.as<int>(), s);
-    sd_scan(icnt, (int)nc1, ioff, sd->aux.as<int>(), s);
+    sfmx_scan(qcnt, false, (int)nc1, qoff, sd->aux.as<int>(), s);
+    sfmx_scan(icnt, false, (int)nc1, ioff, sd->aux.as<int>(), s);
     SFMX_HIP(ctx, hipMemcpyAsync(&items, ioff + sd->ncells, 4, hipMemcpyDeviceToHost, s));
   }
   SFMX_HIP(ctx, hipGetLastError());

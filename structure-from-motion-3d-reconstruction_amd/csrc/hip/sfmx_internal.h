@@ -17,7 +17,7 @@
 // is a deadlock across ranks.  The outgrown block is parked and released with the buffer (growth is geometric, so the parked
 // blocks add up to less than four times the final size).
 #include <vector>
-struct DevBuf {
+template <class Mem> struct Slab {
   void* p = nullptr;
   size_t cap = 0;
   std::vector<void*> parked;
@@ -27,45 +27,41 @@ struct DevBuf {
     p = nullptr;
     cap = 0;
     size_t want = n < 4096 ? 4096 : n + n / 4;
-    hipError_t e = hipMalloc(&p, want);
+    hipError_t e = Mem::alloc(&p, want);
     if (e == hipSuccess) cap = want;
     return e;
   }
   void release() {
-    if (p) (void)hipFree(p);
-    for (void* q : parked) (void)hipFree(q);
+    if (p) (void)Mem::free(p);
+    for (void* q : parked) (void)Mem::free(q);
     parked.clear();
     p = nullptr;
     cap = 0;
   }
   template <class T> T* as() const { return static_cast<T*>(p); }
 };
-
+struct DevMem {
+  static hipError_t alloc(void** p, size_t n) { return hipMalloc(p, n); }
+  static hipError_t free(void* p) { return hipFree(p); }
+};
 // Pinned host memory that kernels read and write directly (track positions, BA poses, polled result blocks): fine-grained
 // coherent and mapped, requested explicitly rather than through the runtime's default for flags == 0.
-struct PinBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  std::vector<void*> parked;
-  hipError_t ensure(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) parked.push_back(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = n < 4096 ? 4096 : n + n / 4;
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocCoherent | hipHostMallocMapped);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    for (void* q : parked) (void)hipHostFree(q);
-    parked.clear();
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T> T* as() const { return static_cast<T*>(p); }
+struct PinMem {
+  static hipError_t alloc(void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocCoherent | hipHostMallocMapped); }
+  static hipError_t free(void* p) { return hipHostFree(p); }
 };
+using DevBuf = Slab<DevMem>;
+using PinBuf = Slab<PinMem>;
+
+// room for `bytes` in a device slab that already holds `used` bytes: a grown slab gets the old contents on stream s (the old
+// block is parked, not freed, so it is still there to copy from)
+static inline hipError_t sfmx_grow_keep(DevBuf& b, size_t used, size_t bytes, hipStream_t s) {
+  if (bytes <= b.cap) return hipSuccess;
+  const void* old = b.p;
+  hipError_t e = b.ensure(bytes + bytes / 2);
+  if (e == hipSuccess && old && used) e = hipMemcpyAsync(b.p, old, used, hipMemcpyDeviceToDevice, s);
+  return e;
+}
 
 // per-kernel profile (only while ctx->timing): accumulated GPU time and launch count of the hot kernels, measured
 // with HIP events recorded on the context's own stream around each launch
@@ -222,3 +218,35 @@ struct KernelTimer {
     }
   }
 };
+
+// event timing of one stage object's launches (sfmx_*_last_us).  The owner zeroes `us` itself: where its call starts, except
+// sfmx_stereo_disparity, which does so after its last synchronise (a failed call keeps the earlier value).  The events are
+// recorded only while ctx->timing, and `us` is set after the stream has been synchronised, only if the query succeeds.
+struct StageTimer {
+  hipEvent_t ev[2] = {};
+  double us = 0.0;
+  hipError_t create() {
+    hipError_t e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    return e;
+  }
+  void destroy() {
+    for (hipEvent_t& e : ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+  hipError_t begin(const sfmx_ctx* c) { return c->timing ? hipEventRecord(ev[0], c->stream) : hipSuccess; }
+  hipError_t end(const sfmx_ctx* c) { return c->timing ? hipEventRecord(ev[1], c->stream) : hipSuccess; }
+  void collect(const sfmx_ctx* c) {  // call after the stream has been synchronised
+    float ms = 0.f;
+    if (c->timing && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) us = (double)ms * 1000.0;
+  }
+};
+
+// scan.hip: exclusive int32 scan of in[0..n), n >= 1, into out (in may equal out), or with popc of the popcounts of in.  One
+// launch per level; aux holds the block sums of every level, sfmx_scan_aux(n) ints.  sfmx_scan_total stores
+// out[n - 1] + value(in[n - 1]), the sum of all n, into *total (device memory) with one more launch.
+size_t sfmx_scan_aux(int n);
+void sfmx_scan(const int* in, bool popc, int n, int* out, int* aux, hipStream_t s);
+void sfmx_scan_total(const int* in, bool popc, const int* out, int n, int* total, hipStream_t s);

@@ -291,8 +291,7 @@ struct sfmx_stereo {
   uint16_t* S = nullptr;
   int16_t* d16 = nullptr;
   int *lab = nullptr, *size = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  double last_us = 0.0;
+  StageTimer t;
 };
 
 const int16_t* sfmx_stereo_device_disp16(const sfmx_stereo* st, int* w, int* h) {
@@ -339,8 +338,7 @@ int sfmx_stereo_create(sfmx_ctx* ctx, int w, int h, const sfmx_stereo_params* p,
                o_S = o_cen + up(2 * n * 8), o_d16 = o_S + up(n * D * 2), o_lab = o_d16 + up(n * 2), o_size = o_lab + up(n * 4),
                total = o_size + up(n * 4);
   hipError_t e = hipMalloc(&st->slab, total);
-  if (e == hipSuccess) e = hipEventCreate(&st->e0);
-  if (e == hipSuccess) e = hipEventCreate(&st->e1);
+  if (e == hipSuccess) e = st->t.create();
   if (e != hipSuccess) {
     sfmx_stereo_destroy(ctx, st);
     return sfmx_fail(ctx, SFMX_ERR_HIP, "sfmx_stereo_create", e);
@@ -365,12 +363,11 @@ void sfmx_stereo_destroy(sfmx_ctx* ctx, sfmx_stereo* st) {
     (void)hipStreamSynchronize(ctx->stream);
   }
   if (st->slab) (void)hipFree(st->slab);
-  if (st->e0) (void)hipEventDestroy(st->e0);
-  if (st->e1) (void)hipEventDestroy(st->e1);
+  st->t.destroy();
   delete st;
 }
 
-double sfmx_stereo_last_us(const sfmx_stereo* st) { return st ? st->last_us : 0.0; }
+double sfmx_stereo_last_us(const sfmx_stereo* st) { return st ? st->t.us : 0.0; }
 
 int sfmx_stereo_disparity(sfmx_ctx* ctx, sfmx_stereo* st, const uint8_t* img_l, const uint8_t* img_r, int on_device, const double* H_l,
                           const double* H_r, int16_t* disp16_out, uint8_t* rect_out, uint16_t* sum_out) {
@@ -390,7 +387,7 @@ int sfmx_stereo_disparity(sfmx_ctx* ctx, sfmx_stereo* st, const uint8_t* img_l, 
   std::memcpy(hl.a, H_l, sizeof hl.a);
   std::memcpy(hr.a, H_r, sizeof hr.a);
   const StereoDims g{w, h, D, st->p.census * st->p.census - 1, st->p.p1, st->p.p2};
-  if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(st->e0, s));
+  SFMX_HIP(ctx, st->t.begin(ctx));
   const dim3 pix((unsigned)((w + 255) / 256), (unsigned)h, 2u);
   k_st_rectify<<<pix, 256, 0, s>>>(il, ir, hl, hr, w, h, st->rect, st->valid);
   k_st_census<<<pix, 256, 0, s>>>(st->rect, st->valid, w, h, st->p.census / 2, st->cen);
@@ -419,16 +416,13 @@ int sfmx_stereo_disparity(sfmx_ctx* ctx, sfmx_stereo* st, const uint8_t* img_l, 
     k_st_uf_apply<<<nb, 256, 0, s>>>((int)n, st->lab, st->size, st->p.speckle_window, st->d16);
   }
   SFMX_HIP(ctx, hipGetLastError());
-  if (ctx->timing) SFMX_HIP(ctx, hipEventRecord(st->e1, s));
+  SFMX_HIP(ctx, st->t.end(ctx));
   SFMX_HIP(ctx, hipMemcpyAsync(disp16_out, st->d16, n * 2, hipMemcpyDeviceToHost, s));
   if (rect_out) SFMX_HIP(ctx, hipMemcpyAsync(rect_out, st->rect, 2 * n, hipMemcpyDeviceToHost, s));
   if (sum_out) SFMX_HIP(ctx, hipMemcpyAsync(sum_out, st->S, n * (size_t)D * 2, hipMemcpyDeviceToHost, s));
   SFMX_HIP(ctx, hipStreamSynchronize(s));
-  st->last_us = 0.0;
-  if (ctx->timing) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, st->e0, st->e1) == hipSuccess) st->last_us = (double)ms * 1000.0;
-  }
+  st->t.us = 0.0;
+  st->t.collect(ctx);
   return SFMX_OK;
 }
 

@@ -3,13 +3,15 @@ faces against the NumPy restatement (tests/fusion_ref.py): a noise slab that rea
 triangle table and shares vertices between cells, volume shapes around the 64 x 4 blocks of the integration and the 1 024-element
 blocks of the scans (up to 1 024^2 grid points and one slice more), trunc / disp_min / min_weight away from their defaults, maps
 holding 0, -1, -32768 and 32767, views of different sizes in one volume (the stack regrown after use), and cameras inside,
-behind and partly beside the volume.  The inputs come from tests/range_inputs.py; tests/test_range_inputs_cpu.py asserts that
+behind and partly beside the volume, and the views that fusion, shade and consist must all refuse.  The inputs come from tests/range_inputs.py; tests/test_range_inputs_cpu.py asserts that
 they hold what these cases rely on."""
 import importlib
 
 import numpy as np
 import pytest
 
+import appearance_ref as AR
+import consist_ref as CR
 import helpers as H
 import range_inputs as RI
 from test_gpu_fusion import _check
@@ -109,3 +111,56 @@ def test_cameras_inside_behind_and_beside(ctx):
         assert ref["count"].any() == (name != "away")
     ref = _case(ctx, VOL, [RI.slab_view(**VOL, seed=1)] + list(special.values()), "all four", trunc=TRUNC)
     assert len(ref["faces"]) > 10000
+
+
+def _bad_views(cam, d16):
+    """(what, cam, map): NaN and inf in each camera field of one good view, and a 1 x 4097 map (w = 4097, one past the limit)"""
+    out = []
+    for bad in (float("nan"), float("inf")):
+        R = np.array(cam["R_rw"], np.float64)
+        R.flat[0] = bad
+        c = np.array(cam["c_left"], np.float64)
+        c[2] = bad
+        out += [(f"R_rw[0] = {bad}", dict(cam, R_rw=R), d16), (f"c_left[2] = {bad}", dict(cam, c_left=c), d16)]
+        out += [(f"{k} = {bad}", dict(cam, **{k: bad}), d16) for k in ("f", "cx", "cy", "B")]
+    return out + [("w = 4097", cam, np.full((1, 4097), 320, np.int16))]
+
+
+def test_view_refusals_agree(ctx):
+    """fusion, shade and consist refuse the same views with SFMX_ERR_INVALID and keep nothing of them: three good 64 x 64
+    sphere views fed afterwards give the reference's bytes in all three (a 9^3 volume, its shaded surface, the filtered maps)"""
+    good = CR.sphere_views(3, 64, 64, 120.0)
+    textured = [(cam, d16, RI.texture(64, 64, k)) for k, (cam, d16) in enumerate(good)]
+    vol = dict(origin=(-0.16, -0.16, -0.16), voxel=0.04, dims=(9, 9, 9))
+    ref = AR.fuse(vol["origin"], vol["voxel"], vol["dims"], textured)
+    cref = CR.filter_views(good, min_support=1)  # three views far apart: few pixels have one supporter, none has two
+    # properties of the input, before the device: a surface, vertices some view sees, pixels kept and pixels dropped
+    assert len(ref["faces"]) > 0 and (ref["vertex_views"] > 0).any() and 0 < cref["kept"].sum() < cref["valid"].sum()
+    fu, sh, cs = ctx.fusion(**vol), ctx.shade(), ctx.consist()
+    for what, cam, d16 in _bad_views(*good[0]):
+        img = np.zeros(d16.shape, np.uint8)
+        for stage, add in (("fusion", lambda: fu.add_view(cam, d16)), ("shade", lambda: sh.add_view(cam, d16, img)),
+                           ("consist", lambda: cs.add_view(cam, d16))):
+            with pytest.raises(capi.SfmxError) as e:
+                add()
+            assert e.value.status == capi.SFMX_ERR_INVALID, f"{stage}: {what}"
+        assert sh.view_count() == 0 and cs.view_count() == 0, what
+    for cam, d16, img in textured:
+        fu.add_view(cam, d16)
+        sh.add_view(cam, d16, img)
+        cs.add_view(cam, d16)
+    assert sh.view_count() == 3 and cs.view_count() == 3
+    _check(fu, ref, "after the refusals")
+    v, f, n = fu.extract_normals()
+    H.assert_bits_equal(v, ref["verts"], "after the refusals: verts")
+    H.assert_bits_equal(n, ref["normals"], "after the refusals: normals")
+    g, c = sh.shade_fusion(fu, len(v), 4.0 * vol["voxel"])
+    assert c.tobytes() == ref["vertex_views"].tobytes() and g.tobytes() == ref["grey"].tobytes(), "after the refusals: shade"
+    cs.filter(min_support=1)
+    valid, kept = cs.counts()
+    assert valid.tobytes() == cref["valid"].tobytes() and kept.tobytes() == cref["kept"].tobytes(), "after the refusals: counters"
+    for i in range(3):
+        d16, sup = cs.read(i)
+        assert d16.tobytes() == cref["disp16"][i].tobytes() and sup.tobytes() == cref["support"][i].tobytes(), f"consist view {i}"
+    for o in (fu, sh, cs):
+        o.close()

@@ -838,6 +838,20 @@ static void ba_normal_equations(const M3& K, const std::vector<M3>& Rwc, const s
   }
 }
 
+// The pose update of one window keyframe from its six entries of dx (rotation, then translation; T:1082-1094)
+static void ba_update_pose(CamPose& pose, const double* dx6) {
+  const P3 w{dx6[0], dx6[1], dx6[2]};
+  const P3 v{dx6[3], dx6[4], dx6[5]};
+  M3 R;
+  P3 t;
+  world_to_cam(pose, R, t);
+  const M3 R2 = m3_mul(rodrigues_exp(w), R);
+  const P3 t2 = add3(t, v);
+  const M3 Rcw = m3_t(R2);
+  pose.R = Rcw;
+  pose.t = neg3(m3_vec(Rcw, t2));
+}
+
 // T:848-1097
 static void bundle_adjust(const M3& K, std::vector<Kf>& kfs, MapSt& map, const BaCfg& cfg) {
   const int N = (int)kfs.size();
@@ -868,18 +882,7 @@ static void bundle_adjust(const M3& K, std::vector<Kf>& kfs, MapSt& map, const B
     for (int li = 0; li < W; li++) world_to_cam(kfs[(size_t)(w0 + li)].pose, Rwc[(size_t)li], twc[(size_t)li]);
     ba_normal_equations(K, Rwc, twc, pts, cfg.huber, cfg.lambda, S, b, true);
     if (!gauss_solve(S, b, D, dx)) return;
-    for (int li = 1; li < W; ++li) {
-      const P3 w{dx[(size_t)6 * li], dx[(size_t)6 * li + 1], dx[(size_t)6 * li + 2]};
-      const P3 v{dx[(size_t)6 * li + 3], dx[(size_t)6 * li + 4], dx[(size_t)6 * li + 5]};
-      M3 R;
-      P3 t;
-      world_to_cam(kfs[(size_t)(w0 + li)].pose, R, t);
-      const M3 R2 = m3_mul(rodrigues_exp(w), R);
-      const P3 t2 = add3(t, v);
-      const M3 Rcw = m3_t(R2);
-      kfs[(size_t)(w0 + li)].pose.R = Rcw;
-      kfs[(size_t)(w0 + li)].pose.t = neg3(m3_vec(Rcw, t2));
-    }
+    for (int li = 1; li < W; ++li) ba_update_pose(kfs[(size_t)(w0 + li)].pose, dx.data() + (size_t)6 * li);
   }
 }
 
@@ -1141,6 +1144,31 @@ void orc_bundle_adjust_window(const double* K9, int n_kf, double* poses12, int n
   for (int k = 0; k < n_kf; k++) {
     std::memcpy(poses12 + 12 * k, kfs[(size_t)k].pose.R.m, 72);
     poses12[12 * k + 9] = kfs[(size_t)k].pose.t.x; poses12[12 * k + 10] = kfs[(size_t)k].pose.t.y; poses12[12 * k + 11] = kfs[(size_t)k].pose.t.z;
+  }
+}
+// The two ends of one iteration of bundle_adjust around orc_ba_build + orc_solve_gauss, by the functions bundle_adjust itself
+// calls: poses12 are camera->world (R row-major, t = centre) as orc_bundle_adjust_window takes them.
+void orc_ba_world_to_cam(const double* poses12, int W, double* poses_wc) {
+  for (int k = 0; k < W; k++) {
+    CamPose p;
+    p.R = m3_from(poses12 + 12 * k);
+    p.t = {poses12[12 * k + 9], poses12[12 * k + 10], poses12[12 * k + 11]};
+    M3 R;
+    P3 t;
+    world_to_cam(p, R, t);
+    std::memcpy(poses_wc + 12 * k, R.m, 72);
+    poses_wc[12 * k + 9] = t.x; poses_wc[12 * k + 10] = t.y; poses_wc[12 * k + 11] = t.z;
+  }
+}
+// poses 1 ... W-1 moved by dx [6W] in place (pose 0 is the gauge, T:1081)
+void orc_ba_apply_update(double* poses12, int W, const double* dx) {
+  for (int k = 1; k < W; k++) {
+    CamPose p;
+    p.R = m3_from(poses12 + 12 * k);
+    p.t = {poses12[12 * k + 9], poses12[12 * k + 10], poses12[12 * k + 11]};
+    ba_update_pose(p, dx + 6 * k);
+    std::memcpy(poses12 + 12 * k, p.R.m, 72);
+    poses12[12 * k + 9] = p.t.x; poses12[12 * k + 10] = p.t.y; poses12[12 * k + 11] = p.t.z;
   }
 }
 void orc_map_iteration_order(int n_pts, int* order) {

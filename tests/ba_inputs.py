@@ -2,6 +2,8 @@
 of its cases.  No files, no device, no oracle at module level: tests/test_ba_inputs_cpu.py runs the CPU oracle on every generator
 and asserts the properties of the inputs that the GPU cases rely on (every kind of point present, both Huber branches taken, the
 boundaries really reached), so that no GPU case can pass on an input that misses its point.
+tests/test_oracle_vs_reference_range.py holds the oracle's bundle_adjust_window to the real reference on every table of this module,
+and ties orc_ba_build (the checker of the kernels) to it.
 
 A problem is the tuple the C ABI takes: poses_wc [W][12] (world -> camera, R row-major | t), K [3][3], X [P][3], CSR
 observation lists obs_ptr [P + 1] / obs_li / obs_uv, plus kinds [P], the kind of every point (see ragged_window).

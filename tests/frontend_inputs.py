@@ -5,6 +5,8 @@ No files, no device, no binding of the device library; the oracle is loaded lazi
 tests/test_frontend_inputs_cpu.py asserts on the CPU the properties of these inputs that the GPU cases rely on (every class present,
 every off-grid branch taken, windows re-staged, levels left early and exhausted, ties really there), so that no GPU case can pass on
 an input that misses its point.
+tests/test_oracle_vs_reference_range.py holds the oracle to the real reference on the pairs, populations, score images and size
+tables of this module.
 
 Coordinates are (x, y) in level-0 pixels.  A pair is two u8 images of one size; a population is xy [N][2] plus labels [N]."""
 from __future__ import annotations

@@ -108,9 +108,12 @@ def ba_problem(W, P, seed, n_kf=None):
 def main():
     r = H.ref()
     assert r is not None, "oracle/_ref/libsfmref.so missing: run `make -C oracle ref` in the build container"
-    if "--e2e-only" not in sys.argv:
+    if "--e2e-only" not in sys.argv and "--large-only" not in sys.argv:
         function_vectors(r)
-    end_to_end()
+    if "--large-only" not in sys.argv:
+        end_to_end()
+    if "--large" in sys.argv or "--large-only" in sys.argv:
+        end_to_end_large()
 
 
 def function_vectors(r):
@@ -300,6 +303,65 @@ def end_to_end():
                             lat=seq["lat"], lon=seq["lon"], names=np.array(seq["names"]), config=np.array(json.dumps(cfg)),
                             stdout=np.array(stdout), **{k.replace(".", "_"): np.array(v) for k, v in files.items()})
         print(name, "->", stdout.strip().splitlines()[-4:])
+
+LARGE_LIMIT_S = 600   # a scenario the reference CLI does not finish in ten minutes is left out (and named in TIMES below)
+
+
+def comparable_part(stdout, files):
+    """what check_e2e_against_reference compares, and no more: stdout, posegraph_edges.csv, keyframes_camera_centers.csv with the
+    x, y, z columns of every row after the gauge keyframe blanked (quirk Q12 leaves them undefined), the PLY header and the
+    number of lines of the PLY file"""
+    rows = files["keyframes_camera_centers.csv"].splitlines()
+    kept = rows[:2]
+    for r in rows[2:]:
+        f = r.split(",")
+        kept.append(",".join(f[:3] + ["", "", ""] + f[6:]))
+    ply = files["templeRing_sparse_points.ply"].splitlines()
+    return dict(stdout=stdout, posegraph_edges_csv=files["posegraph_edges.csv"], keyframes_camera_centers_csv="\n".join(kept) + "\n",
+                ply_header="\n".join(ply[:7]) + "\n", ply_lines=len(ply))
+
+
+def end_to_end_large():
+    """The reference CLI on the generated sequences of tests/pipeline_inputs.py (the sizes tests/test_gpu_pipeline.py runs the
+    device pipeline at) -> tests/golden/e2e_large.json.  No image is stored: the tests render the frames again.  Name scenarios
+    on the command line to run only those; the others keep their entries.
+
+    Wall time of the reference CLI as measured in the build container (one core, x86-64, g++ -O2):
+        vga6 5 s, bench47 62 s, c3_5000 6 s, c5_1080p 31 s -- none is near the limit, so none is left out
+    """
+    import time
+    import pipeline_inputs as PI
+    cli = H.ref_cli()
+    path = os.path.join(HERE, "e2e_large.json")
+    store = json.load(open(path)) if os.path.exists(path) else {}
+    only = [a for a in sys.argv[1:] if a in PI.LARGE]
+    for name in PI.LARGE:
+        if only and name not in only:
+            continue
+        seq = PI.sequence(name)
+        cfg = PI.config_json(name)
+        with tempfile.TemporaryDirectory() as td:
+            synth.write_dataset(td, seq)
+            with open(os.path.join(td, "cfg.json"), "w") as f:
+                json.dump(cfg, f)
+            t0 = time.time()
+            try:
+                p = subprocess.run([cli, td, os.path.join(td, "out"), "--config", os.path.join(td, "cfg.json")],
+                                   capture_output=True, text=True, cwd=td, timeout=LARGE_LIMIT_S)
+            except subprocess.TimeoutExpired:
+                print(name, f"-> left out: the reference CLI ran longer than {LARGE_LIMIT_S} s")
+                store.pop(name, None)
+                continue
+            dt = time.time() - t0
+            assert p.returncode == 0, p.stderr
+            stdout = p.stdout.replace(os.path.join(td, "out"), "<OUT>")
+            files = {fn: open(os.path.join(td, "out", fn)).read() for fn in
+                     ("keyframes_camera_centers.csv", "posegraph_edges.csv", "templeRing_sparse_points.ply")}
+        store[name] = dict(config=cfg, **comparable_part(stdout, files))
+        print(name, f"-> {dt:.0f} s", stdout.strip().splitlines()[-3:])
+        with open(path, "w") as f:
+            json.dump(store, f, indent=1, sort_keys=True)
+            f.write("\n")
 
 
 if __name__ == "__main__":

@@ -9,7 +9,8 @@
 * a plain float64 unblocked Cholesky (the model the bounds are checked against on the CPU, and the pivot test's view of a cut graph);
 * a numpy model of the kernels' schedule: 32-column panels, 64 x 64 lower-triangle tiles under the kernel's linear tile index.
 
-What these inputs reach is asserted by tests/test_posegraph_inputs_cpu.py."""
+What these inputs reach is asserted by tests/test_posegraph_inputs_cpu.py. The pipeline-level graphs (PIPE_KINDS x PIPE_SIZES,
+CUT_CASES, self_edge_only_graph) also go through the real reference: tests/test_oracle_vs_reference_range.py."""
 from __future__ import annotations
 
 import importlib

@@ -21,6 +21,9 @@ Scene classes (second-image noise sigma; 30 % uniform outliers):
   edge                general with planted points a few ulp either side of thr for the winner and the runner-up (_plant_edge)
   nan                 general with two all-NaN points, one drawn by some octet and one by none.  (The reference's Jacobi never picks
                       a NaN pivot, strict '>': a NaN octet yields the finite hypothesis of an unrotated matrix, with a count.)
+
+What is said of the reference here was read off its source; tests/test_oracle_vs_reference_range.py asserts it on the reference
+itself: hypotheses, counts, Sampson errors and find_E_ransac of every class at N0 and at the N_SIZES up to 1000, bit for bit.
 """
 from __future__ import annotations
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import solve_inputs as SI
 
 pytestmark = pytest.mark.gpu
 O = H.oracle()
@@ -517,57 +518,25 @@ def test_solve_dense(ctx, golden):
         H.assert_bits_equal(x, golden[f"sg_x_{n}"], f"solve n={n}")
     rc, _ = ctx.solve_dense(golden["sg_A_sing"], np.ones(5))
     assert rc == capi.SFMX_ERR_SINGULAR
-    rng = np.random.default_rng(9)
-    for n in (1, 2, 33, 96, 128):
-        A = rng.normal(size=(n, n))
-        b = rng.normal(size=n)
-        if n == 33:
-            A[5, :] *= 1e-20  # exercises the |f| < 1e-18 skip
+    cases = SI.dense_random_cases()
+    for name, A, b in cases[:-1]:
         rc, x = ctx.solve_dense(A, b)
         erc, ex = H.solve_gauss(O, "orc", A, b)
         assert (rc != 0) == (erc != 0)
         if rc == 0:
-            H.assert_bits_equal(x, ex, f"random n={n}")
-    A = rng.normal(size=(9, 9))
-    A[4, 4] = np.nan  # NaN propagates instead of throwing, as in the reference
-    rc, x = ctx.solve_dense(A, np.ones(9))
-    erc, ex = H.solve_gauss(O, "orc", A, np.ones(9))
+            H.assert_bits_equal(x, ex, name)
+    name, A, b = cases[-1]  # NaN on the diagonal: it propagates instead of throwing, as in the reference
+    rc, x = ctx.solve_dense(A, b)
+    erc, ex = H.solve_gauss(O, "orc", A, b)
     assert rc == erc == 0
-    H.assert_bits_equal(x, ex, "nan solve", nan_equal=True)
+    H.assert_bits_equal(x, ex, name, nan_equal=True)
 
 
 @pytest.mark.parametrize("n", [36, 60])
 def test_solve_register_kernels_edge_cases(ctx, n):
     """k_solve_regs<36/60> (the BA windows of 6 and 10 poses): random systems, pivot ties (first position wins), the
     |f| < 1e-18 skip, NaN on and off the diagonal, zero columns / singular systems, all against the oracle bit for bit."""
-    rng = np.random.default_rng(100 + n)
-    cases = []
-    for t in range(6):
-        cases.append((f"random {t}", rng.normal(size=(n, n)), rng.normal(size=n)))
-    M = rng.normal(size=(n, n))
-    cases.append(("spd", M @ M.T + 1e-3 * np.eye(n), rng.normal(size=n)))
-    A = rng.integers(-3, 4, size=(n, n)).astype(np.float64)  # many equal |values| per column: ties at most steps
-    cases.append(("integer ties", A + 0.0, rng.integers(-5, 6, size=n).astype(np.float64)))
-    A = rng.normal(size=(n, n))
-    A[:, 0] = np.where(np.arange(n) % 2 == 0, 2.5, -2.5)  # every row ties in the first column, signs differ
-    cases.append(("tie column 0", A, rng.normal(size=n)))
-    A = rng.normal(size=(n, n))
-    A[5, :] *= 1e-20
-    A[n - 2, :] *= 1e-19
-    cases.append(("tiny multipliers", A, rng.normal(size=n)))
-    A = rng.normal(size=(n, n))
-    A[7, 3] = np.nan
-    cases.append(("nan off the diagonal", A, np.ones(n)))
-    A = rng.normal(size=(n, n))
-    A[0, 0] = np.nan
-    cases.append(("nan on the first diagonal element", A, np.ones(n)))
-    A = rng.normal(size=(n, n))
-    A[:, 4] = 0.0
-    cases.append(("zero column", A, np.ones(n)))
-    A = rng.normal(size=(n, n))
-    A[n - 1, :] = A[0, :]
-    cases.append(("duplicate row", A, np.ones(n)))
-    cases.append(("identity with signed zeros", np.eye(n) * -1.0 + 0.0 * rng.normal(size=(n, n)), -np.ones(n)))
+    cases = SI.register_cases(n)
     for name, A, b in cases:
         rc, x = ctx.solve_dense(A, b)
         erc, ex = H.solve_gauss(O, "orc", A, b)
@@ -580,50 +549,38 @@ def test_solve_dense_blocked_sizes(ctx):
     """n > 64 takes the blocked multi-workgroup elimination (pose graphs: 3 unknowns per keyframe).  Bit-exact against the
     oracle's solve_gauss on sizes around the block edges, on a pose-graph-shaped system, with tied pivots, skipped
     multipliers, NaN and a singular matrix deep inside."""
-    rng = np.random.default_rng(21)
-    for n in (65, 96, 97, 141, 300, 513):
-        A = rng.normal(size=(n, n))
-        b = rng.normal(size=n)
-        if n == 97:
-            A[40, :] *= 1e-20          # |f| < 1e-18 skip in the panel, in the block rows and in the trailing update
-            A[:, 70] *= 1e-21
-        if n == 141:
-            A[100] = A[20]             # duplicate rows: tied pivot candidates, later an exactly singular step
-        if n == 300:
-            A = np.round(A * 4) / 4    # many exactly equal |a_ik|: first-maximum rule
+    cases = SI.blocked_cases()
+    for name, A, b in cases[:6]:
         rc, x = ctx.solve_dense(A, b)
         erc, ex = H.solve_gauss(O, "orc", A, b)
-        assert (rc != 0) == (erc != 0), n
+        assert (rc != 0) == (erc != 0), name
         if rc == 0:
-            H.assert_bits_equal(x, ex, f"blocked n={n}")
-    # pose-graph shape: weighted graph Laplacian (x) I3 plus a gauge term, 100 keyframes -> 300 unknowns
-    N = 100
-    L = np.zeros((3 * N, 3 * N))
-    for a in range(N - 1):
-        for c, w in ((a + 1, 400.0 + a), (min(N - 1, a + 7), 90.0)):
-            for d in range(3):
-                L[3 * a + d, 3 * a + d] += w; L[3 * c + d, 3 * c + d] += w
-                L[3 * a + d, 3 * c + d] -= w; L[3 * c + d, 3 * a + d] -= w
-    L[:3, :3] += np.eye(3) * 1e9
-    g = rng.normal(size=3 * N)
+            H.assert_bits_equal(x, ex, name)
+    (_, L, g), (_, An, bn), (_, Ar, br) = cases[6:]
     rc, x = ctx.solve_dense(L, g)
     erc, ex = H.solve_gauss(O, "orc", L, g)
     assert rc == erc == 0
     H.assert_bits_equal(x, ex, "pose-graph system")
-    A = rng.normal(size=(130, 130))
-    A[77, 3] = np.nan
-    rc, x = ctx.solve_dense(A, np.ones(130))
-    erc, ex = H.solve_gauss(O, "orc", A, np.ones(130))
+    rc, x = ctx.solve_dense(An, bn)
+    erc, ex = H.solve_gauss(O, "orc", An, bn)
     assert rc == erc
     if rc == 0:
         H.assert_bits_equal(x, ex, "nan blocked", nan_equal=True)
-    A = rng.normal(size=(200, 200))
-    A[:, 150] = A[:, 10] * 2.0     # rank deficient: the pivot of some step deep inside falls below 1e-15 (or rounding keeps it alive -- same verdict either way)
-    rc, x = ctx.solve_dense(A, np.ones(200))
-    erc, ex = H.solve_gauss(O, "orc", A, np.ones(200))
+    rc, x = ctx.solve_dense(Ar, br)
+    erc, ex = H.solve_gauss(O, "orc", Ar, br)
     assert (rc != 0) == (erc != 0)
     if rc == 0:
         H.assert_bits_equal(x, ex, "rank-deficient blocked", nan_equal=True)
+
+
+def test_solve_skipped_multipliers_decide_bits(ctx):
+    """the |f| < 1e-18 skip on systems that stay solvable, where skipping or not changes the solution (the rows scaled by 1e-20
+    above end singular either way): below, in and above the register kernels"""
+    for name, A, b in SI.skip_cases():
+        rc, x = ctx.solve_dense(A, b)
+        erc, ex = H.solve_gauss(O, "orc", A, b)
+        assert rc == erc == 0, name
+        H.assert_bits_equal(x, ex, name)
 
 
 def test_solve_dense_has_no_size_cliff(ctx, monkeypatch):

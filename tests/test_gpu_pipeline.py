@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import pipeline_inputs as PI
 from test_oracle_golden import check_e2e_against_reference
 
 pytestmark = pytest.mark.gpu
@@ -53,8 +54,7 @@ def test_pipeline_matches_reference_and_oracle(ctx, name, tmp_path):
 
 def test_pipeline_640x480_vs_oracle(ctx, tmp_path):
     """Full-size frames, default reference config, BA + keyframes firing; every output byte vs the oracle."""
-    seq = synth.make_sequence(6, 640, 480, 0.3, n_blobs=20000, seed=7)
-    cfg = dict(H.PIPE_DEFAULTS, frames=6)
+    seq, cfg = PI.sequence("vga6"), H.pipe_cfg_from_json(PI.config_json("vga6"))
     out_g, out_o = str(tmp_path / "gpu"), str(tmp_path / "orc")
     r = pipe.run(ctx, seq["images"], seq["names"], seq["K"], seq["lat"], seq["lon"], cfg, out_g)
     rc, olog, nk, npnt = H.orc_pipeline_run(seq["images"], seq["names"], seq["K"], seq["lat"], seq["lon"], cfg, out_o)
@@ -67,8 +67,7 @@ def test_bench_workload_47_frames_vs_oracle(ctx, tmp_path):
     """BASELINE config 2 == the workload bench.py times: 47 frames 640x480, reference default config (synthetic
     TempleRing-47 stand-in, same generator call and seed as bench.py rank 0).  stdout and all three output files must be
     byte-equal to the oracle's run: the BA window slides past 6 keyframes, lane joins happen at full image size."""
-    seq = synth.make_sequence(47, 640, 480, 0.3, n_blobs=20000, seed=7)
-    cfg = dict(H.PIPE_DEFAULTS, frames=47)
+    seq, cfg = PI.sequence("bench47"), H.pipe_cfg_from_json(PI.config_json("bench47"))
     out_g, out_o = str(tmp_path / "gpu"), str(tmp_path / "orc")
     r = pipe.run(ctx, seq["images"], seq["names"], seq["K"], seq["lat"], seq["lon"], cfg, out_g)
     rc, olog, nk, npnt = H.orc_pipeline_run(seq["images"], seq["names"], seq["K"], seq["lat"], seq["lon"], cfg, out_o)
@@ -140,8 +139,7 @@ def test_pipeline_c3_5000_tracks_vs_oracle(ctx, tmp_path):
     actually reach the KLT kernel."""
     # 0.01 deg/frame: the reference's LK adds ~iters x the true flow per level (it samples I0 and I1 at the same moved
     # coordinates, lk_step T:424-460, SURVEY.md A7), so on this close, frame-filling shell only sub-pixel flow keeps the tracks alive
-    seq = synth.make_sequence(4, 640, 480, 0.01, n_blobs=150000, seed=7, shell_scale=3.5)
-    cfg = dict(H.PIPE_DEFAULTS, frames=4, max_tracks=5000, min_tracks=2045, min_distance=4, kf_parallax_px=1.0)
+    seq, cfg = PI.sequence("c3_5000"), H.pipe_cfg_from_json(PI.config_json("c3_5000"))
     out_g, out_o = str(tmp_path / "gpu"), str(tmp_path / "orc")
     r = pipe.run(ctx, seq["images"], seq["names"], seq["K"], seq["lat"], seq["lon"], cfg, out_g)
     st = r["stats"]
@@ -159,9 +157,8 @@ def test_c5_end_to_end_1080p_loop_closure_posegraph(ctx, tmp_path, monkeypatch):
     dense system (SFMX_POSEGRAPH_SOLVER=dense) stdout and all three files are byte-equal to the oracle's; with the
     structured FP64-MFMA solver (the product path above 6 400 unknowns, forced here) the same keyframes / edges come out
     and the centres agree to 1e-9 of their magnitude."""
-    ang = [0.1 * a for a in (0, 1, 2, 3, 4, 5, 6, 5, 4, 3, 2, 1, 0, 1)]
-    seq = synth.make_sequence(len(ang), 1920, 1080, 0.1, n_blobs=20000, seed=13, angles=ang)
-    cfg = dict(H.PIPE_DEFAULTS, frames=len(ang), kf_min_inliers=100, kf_parallax_px=1.0)
+    ang = PI.C5_ANGLES
+    seq, cfg = PI.sequence("c5_1080p"), H.pipe_cfg_from_json(PI.config_json("c5_1080p"))
     out_o = str(tmp_path / "orc")
     rc, olog, nk, npnt = H.orc_pipeline_run(seq["images"], seq["names"], seq["K"], seq["lat"], seq["lon"], cfg, out_o)
     edges_o = open(os.path.join(out_o, "posegraph_edges.csv")).read().splitlines()

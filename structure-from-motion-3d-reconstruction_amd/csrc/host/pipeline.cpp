@@ -820,15 +820,15 @@ std::optional<RelPose> find_E_ransac_gpu(sfmx_ctx* ctx, const Mat3& K, const std
 }
 
 // ------------------------------------------------------------------------------------------ map
-int MapState::add(int tid, V3 Xw) {
+MapPoint& MapState::add_point(int tid, V3 Xw) {
   const int pid = next_pid++;
   MapPoint mp(pts.get_allocator().arena);
   mp.pid = pid;
   mp.tid = tid;
   mp.Xw = Xw;
-  pts.emplace(pid, std::move(mp));
+  MapPoint& node = pts.emplace(pid, std::move(mp)).first->second;
   tid2pid.emplace(tid, pid);
-  return pid;
+  return node;
 }
 void MapState::add_obs(int tid, int kf_id, V2 uv) {
   auto it = tid2pid.find(tid);
@@ -842,7 +842,8 @@ GpuBundleAdjuster::~GpuBundleAdjuster() {
   else sfmx_ba_destroy(ctx_, prob_);
 }
 
-BaJob GpuBundleAdjuster::gather(const Mat3& K, const std::vector<Keyframe>& kfs, const MapState& map, const BAConfig& cfg) {
+BaJob GpuBundleAdjuster::gather_structure(const Mat3& K, const std::vector<Keyframe>& kfs, const MapState& map, const BAConfig& cfg,
+                                          int first_pending_pid) {
   BaJob job;
   job.K = K;
   job.cfg = cfg;
@@ -874,6 +875,7 @@ BaJob GpuBundleAdjuster::gather(const Mat3& K, const std::vector<Keyframe>& kfs,
       uv.resize(2 * mark);
       continue;
     }
+    if (kv.second.pid >= first_pending_pid) job.await.emplace_back((std::int32_t)P, (std::int32_t)(kv.second.pid - first_pending_pid));
     X.push_back(kv.second.Xw.x); X.push_back(kv.second.Xw.y); X.push_back(kv.second.Xw.z);
     optr.push_back((std::int32_t)oli.size());
     if (++P >= cfg.max_points) break;
@@ -883,10 +885,19 @@ BaJob GpuBundleAdjuster::gather(const Mat3& K, const std::vector<Keyframe>& kfs,
   job.w0 = w0;
   job.W = W;
   job.P = P;
-  job.win.resize((size_t)W);
-  for (int li = 0; li < W; li++) job.win[(size_t)li] = kfs[(size_t)(w0 + li)].pose;
-  job.valid = true;
   return job;
+}
+
+void GpuBundleAdjuster::gather_values(BaJob& job, const std::vector<Keyframe>& kfs, const V3* const* pending_xw) {
+  if (job.P == 0) return;  // no window or no point: stays invalid
+  for (const auto& a : job.await) {
+    const V3& x = *pending_xw[(size_t)a.second];
+    job.X[(size_t)3 * a.first] = x.x; job.X[(size_t)3 * a.first + 1] = x.y; job.X[(size_t)3 * a.first + 2] = x.z;
+  }
+  job.await.clear();
+  job.win.resize((size_t)job.W);
+  for (int li = 0; li < job.W; li++) job.win[(size_t)li] = kfs[(size_t)(job.w0 + li)].pose;
+  job.valid = true;
 }
 
 void GpuBundleAdjuster::solve(BaJob& job) {
@@ -1416,7 +1427,7 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
       for (const char* c = order; *c; ++c) {
         const int role = *c == 'P' ? ContextPool::PREFETCH : *c == 'T' ? ContextPool::TRACKER : *c == 'B' ? ContextPool::LANE_B
                          : *c == 'C' ? ContextPool::LANE_C : *c == 'A' ? ContextPool::LANE_A : *c == 'E' ? ContextPool::LANE_E
-                         : *c == 'a' ? ContextPool::LANE_A2 : 0;  // (two 'P' = both prefetch workers' contexts)
+                         : *c == 'a' ? ContextPool::LANE_A2 : *c == 'e' ? ContextPool::LANE_E2 : 0;  // (two 'P' = both prefetch workers' contexts)
         if (role) made.push_back(ContextPool::instance().acquire(dev, 0, role));
       }
       for (PooledCtx* pc : made) ContextPool::instance().release(pc);
@@ -1522,8 +1533,11 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
   // SFMX_NO_ASYNC=1 runs everything on this thread.
   const bool use_lane = !std::getenv("SFMX_NO_ASYNC");
   PhaseMark pm_lanes{"~lanes B C E.. done", t_all};
-  StageClock lane_clk, lane_c_clk, lane_e_clk;
-  std::unique_ptr<AsyncLane> lane, lane_c, lane_e;
+  StageClock lane_clk, lane_c_clk, lane_e_clk, lane_e2_clk;
+  std::unique_ptr<AsyncLane> lane, lane_c, lane_e, lane_e2;
+  // SFMX_GATHER_LATE=1: a keyframe block inserts its map points and gathers the next BA window after the join with lane B, as
+  // every block with an accepted loop closure does anyway (A/B and tests; identical output).  Read per call.
+  const bool gather_late = std::getenv("SFMX_GATHER_LATE") != nullptr;
   if (use_lane) {
     lane = std::make_unique<AsyncLane>(sfmx_ctx_device(ctx), prio_env("SFMX_PRIO_LANE_B", 0), ContextPool::LANE_B);
     // SFMX_SPIN_B_US: polling window of the ONE hand-off pair on the pass's critical chain -- the geometry thread waiting for BA(k)
@@ -1532,11 +1546,20 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
     lane_c = std::make_unique<AsyncLane>(sfmx_ctx_device(ctx), prio_env("SFMX_PRIO_LANE_C", 0), ContextPool::LANE_C);
     if (!std::getenv("SFMX_NO_EDGE_LANE"))
       lane_e = std::make_unique<AsyncLane>(sfmx_ctx_device(ctx), prio_env("SFMX_PRIO_LANE_E", 0), ContextPool::LANE_E);
+    // Two edge lanes by default: the edges of odd keyframes go to lane E2 (its context is created on first use, after the others,
+    // like lane A2's), so that a call -- ~520 us of lane time -- has two keyframe periods.  With the structural work of a keyframe
+    // block ahead of the join a keyframe period fell under one call, and the pass ended with lane E's backlog
+    // (profiles/gather_early_ab.txt: 36.5 -> 33.4 ms per pass).  SFMX_EDGE_LANES=1|2, read per call.
+    int edge_lanes = 2;
+    if (const char* e = std::getenv("SFMX_EDGE_LANES")) edge_lanes = std::atoi(e);
+    if (lane_e && edge_lanes >= 2)
+      lane_e2 = std::make_unique<AsyncLane>(sfmx_ctx_device(ctx), prio_env("SFMX_PRIO_LANE_E", 0), ContextPool::LANE_E2);
   }
   if (sfmx_get_timing(ctx)) {  // per-kernel event timing is inherited by the helper contexts
     if (lane) (void)sfmx_set_timing(lane->ctx(), 1);
     if (lane_c) (void)sfmx_set_timing(lane_c->ctx(), 1);
     if (lane_e) (void)sfmx_set_timing(lane_e->ctx(), 1);
+    if (lane_e2) (void)sfmx_set_timing(lane_e2->ctx(), 1);
   }
   sfmx_ctx* bctx = lane ? lane->ctx() : ctx;
   StageClock* bclk = lane ? &lane_clk : &clk;
@@ -1564,14 +1587,16 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
     std::optional<RelPose> rel;
     std::uint64_t ticket = 0;
   } pending_loop, queued_loop;
+  BaJob next_ba;  // the job of the keyframe under construction, while pending_ba still belongs to lane B
   struct LaneGuard {  // declared after everything the lanes' tasks reference: drained first when unwinding
-    AsyncLane *l, *m, *e;
+    AsyncLane *l, *m, *e, *e2;
     ~LaneGuard() {
       if (l) { try { l->wait(); } catch (...) {} }
       if (m) { try { m->wait(); } catch (...) {} }
       if (e) { try { e->wait(); } catch (...) {} }
+      if (e2) { try { e2->wait(); } catch (...) {} }
     }
-  } lane_guard{lane.get(), lane_c.get(), lane_e.get()};
+  } lane_guard{lane.get(), lane_c.get(), lane_e.get(), lane_e2.get()};
   sfmx_pyramid* old_pyr = nullptr;  // loop-closure verification image (T:1834)
   struct Guard { sfmx_ctx* c; sfmx_pyramid** p; ~Guard() { if (*p) sfmx_pyramid_destroy(c, *p); } } guard{ctx, &old_pyr};
 
@@ -1588,6 +1613,7 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
   auto flush_edges = [&]() {
     const auto tj = Clock::now();
     if (edge_lane) edge_lane->wait();
+    if (lane_e2) lane_e2->wait();
     clk.join_wait += since(tj);
     for (PendingEdge& pe : pending_edges) {  // keyframe order = the order every rank merges them in
       if (!pe.ra) continue;
@@ -1832,7 +1858,9 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
       clk.bookkeeping += since(tb0);
       // triangulation jobs (T:1801-1813).  The DLT solves (libm Jacobi) are independent: gather the jobs in the reference's
       // iteration order, solve them on the host pool, then insert into the map sequentially in that same order.
-      struct TriJob { int tid; TrackHist* th; const ObsList* hist; const Pose* p0; const Pose* pl; V3 X; bool ok; };
+      // (the two poses by keyframe index: kfs may grow, and BA(k-1) may still be refining them, before the solves read them;
+      // id_l == kf.kf_id names the keyframe under construction until it has been pushed)
+      struct TriJob { int tid; TrackHist* th; const ObsList* hist; int id0, idl; V3 X; bool ok; };
       std::vector<TriJob> jobs;
       const auto th0 = Clock::now();
       if (kfs.size() >= 1) {
@@ -1846,8 +1874,7 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
           // construction is pushed (T:1815), i.e. one past the end of the vector whenever idl is the
           // new keyframe — undefined behaviour whose result is heap garbage.  The defined reading is
           // used here: the new keyframe's own pose.
-          const Pose* pl = (idl < (int)kfs.size()) ? &kfs[(size_t)idl].pose : &kf.pose;
-          jobs.push_back(TriJob{tid, &kv.second, &hist, &kfs[(size_t)id0].pose, pl, V3{}, true});
+          jobs.push_back(TriJob{tid, &kv.second, &hist, id0, idl, V3{}, true});
         }
       }
       clk.tri_iter += since(th0);
@@ -1860,41 +1887,94 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
       if (edge_prev_id >= 0 && ei.size() >= 80) {
         pending_edges.push_back(PendingEdge{edge_prev_id, kf.kf_id, nullptr});
         PendingEdge* slot = &pending_edges.back();  // std::deque: stays valid while later edges are appended
-        auto task = [slot, ectx, eclk, K, ransac_ahead, ei = std::move(ei), ej = std::move(ej)]() {
-          slot->ra = ransac_ahead(ectx, K, ei, ej, 2500, 1e-3, 60, eclk);
+        const bool second = lane_e2 && (kf.kf_id & 1);  // keyframe parity; the slots keep the keyframe order
+        sfmx_ctx* const tctx = second ? lane_e2->ctx() : ectx;
+        StageClock* const tclk = second ? &lane_e2_clk : eclk;
+        auto task = [slot, tctx, tclk, K, ransac_ahead, ei = std::move(ei), ej = std::move(ej)]() {
+          slot->ra = ransac_ahead(tctx, K, ei, ej, 2500, 1e-3, 60, tclk);
         };
-        if (edge_lane) edge_lane->submit(std::move(task));
+        if (second) lane_e2->submit(std::move(task));
+        else if (edge_lane) edge_lane->submit(std::move(task));
         else task();
       }
-      if (kfs.size() >= 1) {
-        // the walk above only reads the track histories; the solves below read the keyframe poses BA(k-1) refines
-        if (!looped) join_b();
+      const int new_kf_id = kf.kf_id;
+      auto solve_jobs = [&](const Pose& new_pose) {  // the DLT solves, on the pool; poses as they are in kfs NOW
         const auto ts0 = Clock::now();
+        const int n_kfs = (int)kfs.size();
         ThreadPool::instance().parallel_for((int)jobs.size(), [&](int i) {
           TriJob& j = jobs[(size_t)i];
-          j.ok = triangulate_dlt(K, *j.p0, *j.pl, j.hist->front().second, j.hist->back().second, j.X);
+          const Pose& pl = j.idl < n_kfs ? kfs[(size_t)j.idl].pose : new_pose;
+          j.ok = triangulate_dlt(K, kfs[(size_t)j.id0].pose, pl, j.hist->front().second, j.hist->back().second, j.X);
         });
         clk.tri_solve += since(ts0);
-        const auto ti0 = Clock::now();
-        for (const TriJob& j : jobs) {
-          if (!j.ok) throw std::runtime_error("Singular K");
-          map.add(j.tid, j.X);
-          j.th->mapped = true;
-          for (const auto& ob : *j.hist) map.add_obs(j.tid, ob.first, ob.second);
-        }
-        clk.tri_insert += since(ti0);
         clk.host += since(ts0);
-      } else if (!looped) {
+        for (const TriJob& j : jobs)
+          if (!j.ok) throw std::runtime_error("Singular K");
+      };
+      if (!looped && !gather_late) {
+        // Structure first: which tracks become map points, their order in the map, their observation lists,
+        // the next window's point selection and observation arrays depend on no pose VALUE, so they are built while BA(k-1) is
+        // still on lane B.  The container operations are exactly those of the other branch, in the same order; the positions
+        // and the window's poses are filled in after the join.
+        std::vector<V3*> xw;  // where each job's position goes: map nodes do not move
+        const bool have_jobs = kfs.size() >= 1;
+        const int first_new_pid = map.next_pid;
+        if (have_jobs) {
+          const auto ti0 = Clock::now();
+          xw.reserve(jobs.size());
+          for (const TriJob& j : jobs) {
+            xw.push_back(&map.add_point(j.tid, V3{}).Xw);
+            j.th->mapped = true;
+            for (const auto& ob : *j.hist) map.add_obs(j.tid, ob.first, ob.second);
+          }
+          clk.tri_insert += since(ti0);
+          clk.host += since(ti0);
+        }
+        kfs.push_back(std::move(kf));
+        kf_desc.push_back(new_desc);
+        last_kf_frame = fi;
+        const auto tg0 = Clock::now();
+        next_ba = GpuBundleAdjuster::gather_structure(K, kfs, map, cfg.ba, first_new_pid);
+        clk.ba_gather += since(tg0);
+        // ---- values: everything below needs BA(k-1)'s poses
         join_b();
+        if (have_jobs) {
+          solve_jobs(kfs[(size_t)new_kf_id].pose);
+          const auto ti1 = Clock::now();
+          for (size_t i = 0; i < jobs.size(); i++) *xw[i] = jobs[i].X;
+          clk.tri_insert += since(ti1);
+          clk.host += since(ti1);
+        }
+        const auto tg1 = Clock::now();
+        GpuBundleAdjuster::gather_values(next_ba, kfs, xw.data());
+        pending_ba = std::move(next_ba);
+        next_ba = BaJob{};
+        clk.ba_gather += since(tg1);
+      } else {
+        if (kfs.size() >= 1) {
+          // the walk above only reads the track histories; the solves below read the keyframe poses BA(k-1) refines
+          if (!looped) join_b();
+          solve_jobs(kf.pose);
+          const auto ti0 = Clock::now();
+          for (const TriJob& j : jobs) {
+            map.add(j.tid, j.X);
+            j.th->mapped = true;
+            for (const auto& ob : *j.hist) map.add_obs(j.tid, ob.first, ob.second);
+          }
+          clk.tri_insert += since(ti0);
+          clk.host += since(ti0);
+        } else if (!looped) {
+          join_b();
+        }
+        kfs.push_back(std::move(kf));
+        kf_desc.push_back(new_desc);
+        last_kf_frame = fi;
+        // T:1820: local BA.  The point/observation gather reads kfs and map now; the device iterations refine a
+        // private copy of the window poses on lane B and are written back at the next join.
+        const auto tg0 = Clock::now();
+        pending_ba = GpuBundleAdjuster::gather(K, kfs, map, cfg.ba);
+        clk.ba_gather += since(tg0);
       }
-      kfs.push_back(std::move(kf));
-      kf_desc.push_back(new_desc);
-      last_kf_frame = fi;
-      // T:1820: local BA.  The point/observation gather reads kfs and map now; the device iterations refine a
-      // private copy of the window poses on lane B and are written back at the next join.
-      const auto tg0 = Clock::now();
-      pending_ba = GpuBundleAdjuster::gather(K, kfs, map, cfg.ba);
-      clk.ba_gather += since(tg0);
       if (lane) lane->submit([&ba, &pending_ba]() { ba.solve(pending_ba); });
       else ba.solve(pending_ba);
       if (!lane) join_lane();
@@ -1942,6 +2022,7 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
     if (lane) clk.grab_profile(lane->ctx());
     if (lane_c) clk.grab_profile(lane_c->ctx());
     if (lane_e) clk.grab_profile(lane_e->ctx());
+    if (lane_e2) clk.grab_profile(lane_e2->ctx());
     if (prefetch) prefetch->grab_profile(clk);
   }
   if (feeder.threaded()) clk.add(feeder.lane_clock());
@@ -1955,8 +2036,14 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
     clk.klt += lane_c_clk.klt; clk.klt_kernel_us += lane_c_clk.klt_kernel_us; clk.lk_steps += lane_c_clk.lk_steps;
     clk.tracks_in += lane_c_clk.tracks_in; clk.klt_calls += lane_c_clk.klt_calls;
   }
+  if (lane_e2) {  // two edge lanes: the busier one is what can bound the pass
+    lane_e_clk.ransac += lane_e2_clk.ransac; lane_e_clk.ransac_kernel_us += lane_e2_clk.ransac_kernel_us; lane_e_clk.ransac_calls += lane_e2_clk.ransac_calls;
+    lane_e_clk.ransac_points += lane_e2_clk.ransac_points; lane_e_clk.ransac_verified += lane_e2_clk.ransac_verified;
+    lane_e_clk.ransac_cert_misses += lane_e2_clk.ransac_cert_misses;
+    lane_e_clk.r_pre += lane_e2_clk.r_pre; lane_e_clk.r_gpu += lane_e2_clk.r_gpu; lane_e_clk.r_verify += lane_e2_clk.r_verify; lane_e_clk.r_decomp += lane_e2_clk.r_decomp;
+  }
   if (lane_e) {
-    clk.lane_e_busy = lane_e->busy_seconds();
+    clk.lane_e_busy = std::max(lane_e->busy_seconds(), lane_e2 ? lane_e2->busy_seconds() : 0.0);
     lane_clk.ransac += lane_e_clk.ransac; lane_clk.ransac_kernel_us += lane_e_clk.ransac_kernel_us; lane_clk.ransac_calls += lane_e_clk.ransac_calls;
     lane_clk.ransac_points += lane_e_clk.ransac_points; lane_clk.ransac_verified += lane_e_clk.ransac_verified;
     lane_clk.ransac_cert_misses += lane_e_clk.ransac_cert_misses;

@@ -113,7 +113,7 @@ struct PooledCtx {
 class ContextPool {
  public:
   static ContextPool& instance();
-  enum Role { PREFETCH = 1, TRACKER = 2, LANE_B = 3, LANE_C = 4, LANE_A = 5, LANE_E = 6, LANE_A2 = 7 };
+  enum Role { PREFETCH = 1, TRACKER = 2, LANE_B = 3, LANE_C = 4, LANE_A = 5, LANE_E = 6, LANE_A2 = 7, LANE_E2 = 8 };
   PooledCtx* acquire(int device, int priority, int role);
   void release(PooledCtx* pc);  // synchronises the context; the caller's threads must have stopped using it
   void clear();
@@ -391,7 +391,8 @@ struct MapState {
       : tid2pid(0, std::hash<int>(), std::equal_to<int>(), ArenaAlloc<std::pair<const int, int>>(a)),
         pts(0, std::hash<int>(), std::equal_to<int>(), ArenaAlloc<std::pair<const int, MapPoint>>(a)) {}
   bool has(int tid) const { return tid2pid.find(tid) != tid2pid.end(); }
-  int add(int tid, V3 Xw);
+  int add(int tid, V3 Xw) { return add_point(tid, Xw).pid; }
+  MapPoint& add_point(int tid, V3 Xw);  // the new node; it never moves (unordered_map), so &Xw stays valid while the map lives
   void add_obs(int tid, int kf_id, V2 uv);
 };
 struct PGEdge {
@@ -414,6 +415,8 @@ struct BaJob {
   std::vector<double> X, uv;
   std::vector<std::int32_t> optr, oli;
   std::vector<Pose> win;  // the window's camera->world poses; refined in place by solve()
+  // gather_structure() only: (point slot, pending index) of the selected points whose position is not known yet
+  std::vector<std::pair<std::int32_t, std::int32_t>> await;
 };
 class GpuBundleAdjuster {
  public:
@@ -422,7 +425,19 @@ class GpuBundleAdjuster {
   GpuBundleAdjuster(sfmx_ctx* ctx, StageClock* clk, sfmx_comm* comm = nullptr, sfmx_ba_problem** keep = nullptr)
       : ctx_(ctx), clk_(clk), comm_(comm), prob_(keep ? *keep : nullptr), keep_(keep) {}
   ~GpuBundleAdjuster();
-  static BaJob gather(const Mat3& K, const std::vector<Keyframe>& kfs, const MapState& map, const BAConfig& cfg);
+  static BaJob gather(const Mat3& K, const std::vector<Keyframe>& kfs, const MapState& map, const BAConfig& cfg) {
+    BaJob j = gather_structure(K, kfs, map, cfg);
+    gather_values(j, kfs, nullptr);
+    return j;
+  }
+  // gather in two halves, so that the first can run while the previous job is still on its lane.
+  //   gather_structure: everything that depends on no pose and no position VALUE -- window, point selection in the map's
+  //     iteration order, optr / oli / uv.  Map points with pid >= first_pending_pid have a placeholder position: they are
+  //     recorded in job.await as (slot, pid - first_pending_pid).  The job is not valid yet.
+  //   gather_values: X of the awaited slots from pending_xw[pending index], the window's poses from kfs; valid from here on.
+  static BaJob gather_structure(const Mat3& K, const std::vector<Keyframe>& kfs, const MapState& map, const BAConfig& cfg,
+                                int first_pending_pid = 0x7fffffff);
+  static void gather_values(BaJob& job, const std::vector<Keyframe>& kfs, const V3* const* pending_xw);
   void solve(BaJob& job);
   static void apply(const BaJob& job, std::vector<Keyframe>& kfs);
   void run(const Mat3& K, std::vector<Keyframe>& kfs, MapState& map, const BAConfig& cfg) {

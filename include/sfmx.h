@@ -38,6 +38,8 @@ typedef struct sfmx_pyramid sfmx_pyramid;
 int sfmx_ctx_create(int device_id, sfmx_ctx** out);
 /* same, with a stream priority hint: <0 high (short latency-critical launches), 0 normal, >0 low (background) */
 int sfmx_ctx_create_prio(int device_id, int priority, sfmx_ctx** out);
+/* (include/sfmx_ctx_split.h: the same in steps -- a context without streams, then each stream -- for the host pipeline, which
+ * interleaves the stream creations of its helper contexts to place them on the hardware queues) */
 void sfmx_ctx_destroy(sfmx_ctx* ctx);
 const char* sfmx_last_error(const sfmx_ctx* ctx);
 int sfmx_sync(sfmx_ctx* ctx);

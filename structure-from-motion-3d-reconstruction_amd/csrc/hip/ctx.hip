@@ -1,5 +1,6 @@
 // ctx.hip — context lifetime, error strings, debug hooks.
 #include "sfmx_internal.h"
+#include "../../../include/sfmx_ctx_split.h"
 
 int sfmx_fail(sfmx_ctx* ctx, int status, const char* what, hipError_t e) {
   if (ctx) {
@@ -16,7 +17,25 @@ extern "C" {
 
 int sfmx_ctx_create(int device_id, sfmx_ctx** out) { return sfmx_ctx_create_prio(device_id, 0, out); }
 
+// HIP hands streams to its hardware queues in creation order: GPU_MAX_HW_QUEUES of them, 8 where the CLI and bench.py find the
+// variable unset, whatever the environment set otherwise (4 on the machines this is measured on).  With the copy stream
+// created FIRST and eight queues, the compute streams of the five pipeline contexts land on queues that do not share with
+// each other (only lane C, which the geometry lane waits for anyway, doubles up with it); the opposite order puts the BA lane
+// next to the prefetch lane and costs 15-20 % keyframes/s (measured on MI355X).  With four queues such pairs put
+// nine compute streams on two queues, lanes C, E and A2 on the BA lane's; the pipeline then creates its helper contexts' streams
+// one by one (sfmx_ctx_create_bare / sfmx_ctx_create_stream, csrc/host/lane_plan.hpp).
 int sfmx_ctx_create_prio(int device_id, int priority, sfmx_ctx** out) {
+  const int rc = sfmx_ctx_create_bare(device_id, priority, out);
+  if (rc != SFMX_OK) return rc;
+  if (sfmx_ctx_create_stream(*out, SFMX_STREAM_COPY) != SFMX_OK || sfmx_ctx_create_stream(*out, SFMX_STREAM_COMPUTE) != SFMX_OK) {
+    sfmx_ctx_destroy(*out);
+    *out = nullptr;
+    return SFMX_ERR_HIP;
+  }
+  return SFMX_OK;
+}
+
+int sfmx_ctx_create_bare(int device_id, int priority, sfmx_ctx** out) {
   if (!out) return SFMX_ERR_INVALID;
   *out = nullptr;
   int n = 0;
@@ -27,25 +46,29 @@ int sfmx_ctx_create_prio(int device_id, int priority, sfmx_ctx** out) {
   // priority: <0 latency-critical chains of tiny kernels (BA), >0 background work with large grids (corner prefetch)
   int lo = 0, hi = 0;  // HIP: numerically lower = higher priority; range [hi, lo]
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-  const int prio = priority < 0 ? hi : (priority > 0 ? lo : (lo + hi) / 2);
-  // HIP hands streams to its hardware queues (GPU_MAX_HW_QUEUES, set to 8 by the CLI and bench.py) in creation order.
-  // With the copy stream created FIRST, the compute streams of the five pipeline contexts land on queues that do not
-  // share with each other (only lane C, which the geometry lane waits for anyway, doubles up with it); the opposite order
-  // puts the BA lane next to the prefetch lane and costs 15-20 % keyframes/s (measured on MI355X).
-  if (hipStreamCreateWithPriority(&c->copy_stream, hipStreamNonBlocking, prio) != hipSuccess ||
-      hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio) != hipSuccess ||
-      hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
-    delete c;
+  c->stream_prio = priority < 0 ? hi : (priority > 0 ? lo : (lo + hi) / 2);
+  if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
+    sfmx_ctx_destroy(c);
     return SFMX_ERR_HIP;
   }
   *out = c;
   return SFMX_OK;
 }
 
+int sfmx_ctx_create_stream(sfmx_ctx* c, int which) {
+  if (!c) return SFMX_ERR_INVALID;
+  SFMX_REQUIRE(c, which == SFMX_STREAM_COMPUTE || which == SFMX_STREAM_COPY);
+  hipStream_t& s = which == SFMX_STREAM_COMPUTE ? c->stream : c->copy_stream;
+  SFMX_REQUIRE(c, s == nullptr);
+  SFMX_HIP(c, hipSetDevice(c->device));
+  SFMX_HIP(c, hipStreamCreateWithPriority(&s, hipStreamNonBlocking, c->stream_prio));
+  return SFMX_OK;
+}
+
 void sfmx_ctx_destroy(sfmx_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);  // a bare context may have no stream yet
   sfmx_release_graphs(c);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   for (auto& b : c->d) b.release();

@@ -75,6 +75,7 @@ struct sfmx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t copy_stream = nullptr;  // speculative D2H that must not delay the compute stream
+  int stream_prio = 0;                // HIP priority both streams are created with (sfmx_ctx_create_stream)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timing = false;
   double last_us = 0.0;

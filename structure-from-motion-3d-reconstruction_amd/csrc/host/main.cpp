@@ -199,7 +199,8 @@ void echo_line(const std::string& s) { std::cout << s; }
 }  // namespace
 
 int main(int argc, char** argv) {
-  // the pipeline keeps five streams busy; HIP's default of 4 hardware queues makes lanes share one
+  // the pipeline keeps ten contexts' streams busy; eight hardware queues where the environment sets no count.  A
+  // count that is set stays: the pipeline reads it and orders its stream creations for it (lane_plan.hpp; four is planned for)
   setenv("GPU_MAX_HW_QUEUES", "8", 0);
   try {
     if (argc < 3) {

@@ -6,6 +6,13 @@
 #include "stereo.hpp"
 #include "introsort_replay.hpp"
 #include "thread_pool.hpp"
+#include "lane_plan.hpp"
+#include "sfmx_ctx_split.h"
+// The split entry points of libsfmx.so are weak references here: the CPU stand-in of the test suite has no streams and no
+// hardware queues and does not export them; every context of a plan is then made whole at its first step, and the plan line
+// (SFMX_LANE_PLAN_PRINT, sfmx_host_lane_plan) says that the order is not in effect.
+#pragma weak sfmx_ctx_create_bare
+#pragma weak sfmx_ctx_create_stream
 
 #include <algorithm>
 #include <chrono>
@@ -296,12 +303,32 @@ PooledCtx* ContextPool::acquire(int device, int priority, int role) {
         return pc;
       }
   }
+  return create(device, priority, role, false);
+}
+PooledCtx* ContextPool::create(int device, int priority, int role, bool bare) {
   auto pc = std::make_unique<PooledCtx>();
   pc->device = device;
   pc->priority = priority;
   pc->role = role;
-  check(nullptr, sfmx_ctx_create_prio(device, priority, &pc->ctx), "ctx_create(helper)");
+  if (bare) check(nullptr, sfmx_ctx_create_bare(device, priority, &pc->ctx), "ctx_create_bare(helper)");
+  else check(nullptr, sfmx_ctx_create_prio(device, priority, &pc->ctx), "ctx_create(helper)");
   return pc.release();
+}
+void ContextPool::discard(PooledCtx* pc) {
+  if (!pc) return;
+  pc->free_pyramids();
+  sfmx_ctx_destroy(pc->ctx);
+  delete pc;
+}
+void ContextPool::warm_up_again(int device) {
+  std::lock_guard<std::mutex> lk(mu_);
+  warmed_.erase(std::remove(warmed_.begin(), warmed_.end(), device), warmed_.end());
+}
+bool ContextPool::warm_up_due(int device) {
+  std::lock_guard<std::mutex> lk(mu_);
+  if (std::find(warmed_.begin(), warmed_.end(), device) != warmed_.end()) return false;
+  warmed_.push_back(device);
+  return true;
 }
 void ContextPool::release(PooledCtx* pc) {
   if (!pc) return;
@@ -325,6 +352,7 @@ void ContextPool::clear() {
     delete pc;
   }
   free_.clear();
+  warmed_.clear();
 }
 void PooledCtx::free_pyramids() {
   if (ba) sfmx_ba_destroy(ctx, ba);
@@ -1395,6 +1423,69 @@ void FrameFeeder::release_upto(int frame) {
   cv_rel_.notify_all();
 }
 
+// ------------------------------------------------------------------------------------------ warm-up by plan
+static std::mutex g_plan_mu;
+static std::string g_plan_line;  // lane_plan::describe of the last warm-up (sfmx_host_lane_plan)
+
+// Helper contexts are created in a fixed order, because the order is the placement on the hardware queues (lane_plan.hpp):
+//   GPU_MAX_HW_QUEUES = 4 (or unset, the runtime's default)  stream by stream, so that the compute streams spread over all four
+//       queues and lane B shares its queue with one edge lane only (plan as8); whole pairs put lanes C, E and A2 on lane B's
+//       queue, and every BA launch then waits behind their RANSAC kernels (profiles/lane_plan_ab.txt);
+//   any other count  whole pairs in the order T(racker) B P(refetch) C A E, and P2, A2, E2 on first use -- all 24 orders of
+//       T B P C were measured on MI355X with GPU_MAX_HW_QUEUES=8 (705-877 keyframes/s; the BA lane must not end up on the
+//       geometry lane's queue, which is where the fourth context goes).
+// SFMX_LANE_PLAN names another plan or spells one out; SFMX_LANE_ORDER (letters, whole pairs) overrides both, as it always did.
+static void warm_up_helper_contexts(int dev) {
+  namespace lp = lane_plan;
+  ContextPool& pool = ContextPool::instance();
+  const int queues = lp::queue_count(std::getenv("GPU_MAX_HW_QUEUES"));
+  std::string line;
+  std::vector<PooledCtx*> made;
+  try {
+  if (const char* order = std::getenv("SFMX_LANE_ORDER")) {
+    for (const char* c = order; *c; ++c) {
+      const int role = *c == 'P' ? ContextPool::PREFETCH : *c == 'T' ? ContextPool::TRACKER : *c == 'B' ? ContextPool::LANE_B
+                       : *c == 'C' ? ContextPool::LANE_C : *c == 'A' ? ContextPool::LANE_A : *c == 'E' ? ContextPool::LANE_E
+                       : *c == 'a' ? ContextPool::LANE_A2 : *c == 'e' ? ContextPool::LANE_E2 : 0;  // (two 'P' = both prefetch workers' contexts)
+      if (role) made.push_back(pool.acquire(dev, 0, role));
+    }
+    line = std::string("order (SFMX_LANE_ORDER) queues=") + std::to_string(queues) + " order=" + order;
+  } else {
+    const lp::Plan plan = lp::choose(queues, std::getenv("SFMX_LANE_PLAN"));
+    if (!plan.message.empty()) std::fprintf(stderr, "sfmx: %s\n", plan.message.c_str());
+    static const int pool_role[lp::kRoles] = {ContextPool::PREFETCH, ContextPool::TRACKER, ContextPool::LANE_B, ContextPool::LANE_C, ContextPool::LANE_A,
+                                              ContextPool::LANE_E,   ContextPool::PREFETCH, ContextPool::LANE_A2, ContextPool::LANE_E2};
+    const bool split = sfmx_ctx_create_bare && sfmx_ctx_create_stream;
+    PooledCtx* of_role[lp::kRoles] = {};
+    for (size_t i = 0; i < plan.warm.size(); ++i) {
+      const lp::Step st = plan.warm[i];
+      PooledCtx*& pc = of_role[st.role];
+      if (!pc) {
+        // a (copy, compute) pair side by side is the one call it always was
+        const bool pair = st.kind == lp::COPY && i + 1 < plan.warm.size() && plan.warm[i + 1] == lp::Step{st.role, lp::COMPUTE};
+        pc = pool.create(dev, 0, pool_role[st.role], split && !pair);
+        made.push_back(pc);
+        if (pair) ++i;
+        if (pair || !split) continue;
+      } else if (!split) {
+        continue;
+      }
+      check(pc->ctx, sfmx_ctx_create_stream(pc->ctx, st.kind == lp::COMPUTE ? SFMX_STREAM_COMPUTE : SFMX_STREAM_COPY), "ctx_create_stream(helper)");
+    }
+    line = lp::describe(plan, queues);
+    if (!split) line += " (NOT in effect: this libsfmx has no split context creation, every context was made as a whole pair at its first step)";
+  }
+  } catch (...) {  // a context may have one stream or none: none of them goes into the pool, and the next run warms up again
+    for (PooledCtx* pc : made) pool.discard(pc);
+    pool.warm_up_again(dev);
+    throw;
+  }
+  for (PooledCtx* pc : made) pool.release(pc);
+  if (std::getenv("SFMX_LANE_PLAN_PRINT")) std::fprintf(stderr, "sfmx lane plan: %s\n", line.c_str());
+  std::lock_guard<std::mutex> lk(g_plan_mu);
+  g_plan_line = line;
+}
+
 void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>& meta, const Mat3& K, const PipelineConfig& cfg,
                   PipelineResult& out, void (*echo)(const std::string&)) {
   const auto t_all = Clock::now();
@@ -1409,29 +1500,13 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
   // one worker keeps frame f+1 in flight; more (SFMX_PREFETCH_WORKERS) remove the residual wait but the extra
   // contexts slow the other lanes down by more than that on one GPU (measured: 1 -> 552, 2 -> 498, 3 -> 510 kf/s)
   // Stream creation order decides which hardware queue a lane's stream lands on (csrc/hip/ctx.hip), and the pool hands
-  // every lane the same context again on later runs.  The helper contexts are therefore created up front, in a fixed
-  // order, the first time a device is used: T(racker) B P(refetch) C -- all 24 orders were measured on MI355X with
-  // GPU_MAX_HW_QUEUES=8 (705-877 keyframes/s; the BA lane must not end up on the geometry lane's queue, which is where the
-  // fourth context goes).  SFMX_LANE_ORDER overrides it for experiments.
+  // every lane the same context again on later runs.  The helper contexts are therefore created up front, by a plan, the
+  // first time a device is used and again after sfmx_host_release_contexts (warm_up_helper_contexts above).
   {
-    static std::mutex once_mu;
-    static std::vector<int> warmed_devices;
+    static std::mutex once_mu;  // a second pipeline on the device waits for the warm-up rather than creating lanes in between
     std::lock_guard<std::mutex> lk(once_mu);
-    const int dev = sfmx_ctx_device(ctx);
-    if (std::find(warmed_devices.begin(), warmed_devices.end(), dev) == warmed_devices.end() && !std::getenv("SFMX_NO_ASYNC") &&
-        !std::getenv("SFMX_NO_CTX_POOL")) {
-      warmed_devices.push_back(dev);
-      const char* order = std::getenv("SFMX_LANE_ORDER");
-      if (!order) order = "TBPCAE";
-      std::vector<PooledCtx*> made;
-      for (const char* c = order; *c; ++c) {
-        const int role = *c == 'P' ? ContextPool::PREFETCH : *c == 'T' ? ContextPool::TRACKER : *c == 'B' ? ContextPool::LANE_B
-                         : *c == 'C' ? ContextPool::LANE_C : *c == 'A' ? ContextPool::LANE_A : *c == 'E' ? ContextPool::LANE_E
-                         : *c == 'a' ? ContextPool::LANE_A2 : *c == 'e' ? ContextPool::LANE_E2 : 0;  // (two 'P' = both prefetch workers' contexts)
-        if (role) made.push_back(ContextPool::instance().acquire(dev, 0, role));
-      }
-      for (PooledCtx* pc : made) ContextPool::instance().release(pc);
-    }
+    if (!std::getenv("SFMX_NO_ASYNC") && !std::getenv("SFMX_NO_CTX_POOL") && ContextPool::instance().warm_up_due(sfmx_ctx_device(ctx)))
+      warm_up_helper_contexts(sfmx_ctx_device(ctx));
   }
   // one worker's 0.9 ms per frame was the tracker lane's bound at 640x480 (it waited 26 of 52 ms for corners): two there.  At
   // 1920x1080 a frame has ~600 k candidates and the tie-order replay on the worker's resolver thread takes milliseconds: with two
@@ -1546,8 +1621,8 @@ void run_pipeline(sfmx_ctx* ctx, FrameSource& src, const std::vector<FrameMeta>&
     lane_c = std::make_unique<AsyncLane>(sfmx_ctx_device(ctx), prio_env("SFMX_PRIO_LANE_C", 0), ContextPool::LANE_C);
     if (!std::getenv("SFMX_NO_EDGE_LANE"))
       lane_e = std::make_unique<AsyncLane>(sfmx_ctx_device(ctx), prio_env("SFMX_PRIO_LANE_E", 0), ContextPool::LANE_E);
-    // Two edge lanes by default: the edges of odd keyframes go to lane E2 (its context is created on first use, after the others,
-    // like lane A2's), so that a call -- ~520 us of lane time -- has two keyframe periods.  With the structural work of a keyframe
+    // Two edge lanes by default: the edges of odd keyframes go to lane E2 (at four hardware queues its context is part of the
+    // warm-up plan; at any other count it is created on first use, after the others, like lane A2's), so that a call -- ~520 us of lane time -- has two keyframe periods.  With the structural work of a keyframe
     // block ahead of the join a keyframe period fell under one call, and the pass ended with lane E's backlog
     // (profiles/gather_early_ab.txt: 36.5 -> 33.4 ms per pass).  SFMX_EDGE_LANES=1|2, read per call.
     int edge_lanes = 2;
@@ -2300,6 +2375,14 @@ int sfmx_pipeline_run_ex(sfmx_ctx* ctx, const std::uint8_t* images_host, const v
 
 // frees the helper contexts kept for reuse by later sfmx_pipeline_run calls
 void sfmx_host_release_contexts() { sfmx_host::ContextPool::instance().clear(); }
+// The creation plan of the last warm-up in this process, as SFMX_LANE_PLAN_PRINT=1 prints it ("as8 (default) queues=4 order=T+ A+ ...");
+// empty before the first run.  The pointer stays valid until the next warm-up.
+const char* sfmx_host_lane_plan() {
+  static std::string out;
+  std::lock_guard<std::mutex> lk(sfmx_host::g_plan_mu);
+  out = sfmx_host::g_plan_line;
+  return out.c_str();
+}
 
 // find_E_ransac seam (T:646-761) on its own, for the parity tests: 1 = pose found, 0 = none (T:648, T:678), < 0 = -status
 int sfmx_host_find_E_ransac(sfmx_ctx* ctx, const double* K9, const double* pi, const double* pj, int n, int iters, double thr, int min_inliers,

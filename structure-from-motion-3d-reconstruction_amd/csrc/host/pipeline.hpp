@@ -115,12 +115,18 @@ class ContextPool {
   static ContextPool& instance();
   enum Role { PREFETCH = 1, TRACKER = 2, LANE_B = 3, LANE_C = 4, LANE_A = 5, LANE_E = 6, LANE_A2 = 7, LANE_E2 = 8 };
   PooledCtx* acquire(int device, int priority, int role);
+  // a new entry, never a pooled one; bare: without streams, which the warm-up then creates one by one (lane_plan.hpp)
+  PooledCtx* create(int device, int priority, int role, bool bare);
   void release(PooledCtx* pc);  // synchronises the context; the caller's threads must have stopped using it
-  void clear();
+  void clear();                 // the next run warms the pool up again
+  bool warm_up_due(int device);  // true once per device and again after clear(): the caller then creates the helper contexts
+  void warm_up_again(int device);  // a warm-up that failed half way: the next run tries again
+  void discard(PooledCtx* pc);     // destroys an entry that was never released into the pool (it may lack streams)
 
  private:
   std::mutex mu_;
   std::vector<PooledCtx*> free_;
+  std::vector<int> warmed_;
 };
 
 // A detection whose tie order still has to be resolved on the host (no device access needed any more): the survivors

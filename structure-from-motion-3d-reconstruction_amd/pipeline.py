@@ -449,7 +449,13 @@ def load_host_library() -> ctypes.CDLL:
         _host = ctypes.CDLL(HOST_LIB_PATH)
         _host.sfmx_host_hypot.restype = c_double
         _host.sfmx_host_hypot.argtypes = [c_double, c_double]
+        _host.sfmx_host_lane_plan.restype = ctypes.c_char_p
     return _host
+
+
+def lane_plan() -> str:
+    """The stream creation plan of the last warm-up of the helper contexts in this process ('' before the first run)."""
+    return load_host_library().sfmx_host_lane_plan().decode()
 
 
 def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=None, cfg: dict | None = None,

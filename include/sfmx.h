@@ -558,6 +558,67 @@ double sfmx_raycast_last_us(const sfmx_raycast* rc);
 /* samples the last render evaluated (inside the grid, up to each ray's hit), counted on the device; 0 before a render */
 uint64_t sfmx_raycast_last_samples(const sfmx_raycast* rc);
 
+/* ---- registering a view to the volume: direct TSDF pose alignment ----------------------------------------- */
+/* The pixels (stride i, stride j) of a view's disparity map are lifted to world points X with the view's pose (the integration's
+ * own lift); a sample is used when its disparity counts (not -16, >= disp_min), X lies inside the grid with all 8 corners of its
+ * cell defined (count >= min_weight) and the interpolated signed distance s has |s| < 1.  With the volume's gradient G
+ * interpolated the same way, gw = G / voxel, the pivot p = the box centre and q = X - p, the row of the sample is
+ * J = (q x gw, gw).  One evaluation gives 28 sums over the samples in one fixed order: A_mn = sum J_m J_n for m <= n (21, row by
+ * row), b_m = sum J_m s (6), e = sum s^2 (1), and n, the samples used.  A Gauss-Newton step solves (A + damping I) delta = -b by
+ * Cholesky on the host and applies delta = (omega, v) as a rotation about p (Cayley: rational, no trigonometry) and a
+ * translation.  Everything is IEEE double in one fixed expression order and the sums are one fixed tree, so sums, n and every
+ * iterate are bit-identical to the NumPy restatement in tests/align_ref.py. */
+#define SFMX_ALIGN_ITERS_CAP 64 /* max_iters, and the length of the trace */
+enum { SFMX_ALIGN_CONVERGED = 0, SFMX_ALIGN_MAX_ITERS = 1, SFMX_ALIGN_TOO_FEW = 2, SFMX_ALIGN_DEGENERATE = 3 };
+typedef struct sfmx_align sfmx_align;  /* device work buffers; they grow on demand and are kept */
+typedef struct sfmx_align_params {
+  int max_iters;    /* evaluations at most, 1 .. 64 (default 10) */
+  int stride;       /* every stride-th pixel of every stride-th row is a sample, >= 1 (default 1) */
+  double disp_min;  /* disparities below this (pixels) are not used (default 1.0); finite */
+  int min_weight;   /* a grid point is defined when count >= min_weight; 0 (default) = the volume's own */
+  int min_pixels;   /* fewer used samples than this end the loop with TOO_FEW, >= 1 (default 64) */
+  double damping;   /* added to the diagonal of A, >= 0 (default 0) */
+  double eps_rot;   /* converged when |omega| <= eps_rot (radians to first order; default 1e-6) ... */
+  double eps_trans; /* ... and |v| <= eps_trans * voxel (default 1e-4) */
+} sfmx_align_params;
+typedef struct sfmx_align_result {
+  sfmx_fusion_view view; /* the refined view: R_rw and c_left move, f, cx, cy, B, w, h are the input's */
+  int status;            /* SFMX_ALIGN_CONVERGED, _MAX_ITERS, _TOO_FEW (n < min_pixels) or _DEGENERATE (a Cholesky pivot <= 0) */
+  int iterations;        /* evaluations made */
+  int32_t n[SFMX_ALIGN_ITERS_CAP];   /* per evaluation: samples used ... */
+  double e[SFMX_ALIGN_ITERS_CAP];     /* ... sum s^2 ... */
+  double rot[SFMX_ALIGN_ITERS_CAP];   /* ... |omega| of the step taken (0 when none was) ... */
+  double trans[SFMX_ALIGN_ITERS_CAP]; /* ... and |v| */
+} sfmx_align_result;
+void sfmx_align_default_params(sfmx_align_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_align_check_params(const sfmx_align_params* p);
+int sfmx_align_create(sfmx_ctx* ctx, sfmx_align** out);
+void sfmx_align_destroy(sfmx_ctx* ctx, sfmx_align* al);
+/* one evaluation at the given view, no step: integrates fu's pending views (as sfmx_fusion_extract does), then sums double [28]
+ * (A row by row upper, b, e) and *n.  disp16 int16 [h][w] (x 16, -16 = invalid), a host pointer or (on_device = 1) a device one */
+int sfmx_align_system(sfmx_ctx* ctx, sfmx_align* al, sfmx_fusion* fu, const sfmx_fusion_view* view, const int16_t* disp16, int on_device,
+                      const sfmx_align_params* p, double* sums, int32_t* n);
+/* the same for any volume: sum double / count int32 [nz][ny][nx], host pointers (copied) or (volume_on_device = 1) device
+ * pointers (read in place); vol gives origin, voxel, nx, ny, nz and min_weight and is checked by sfmx_fusion_check_params */
+int sfmx_align_system_arrays(sfmx_ctx* ctx, sfmx_align* al, const sfmx_fusion_params* vol, const double* sum, const int32_t* count,
+                             int volume_on_device, const sfmx_fusion_view* view, const int16_t* disp16, int on_device,
+                             const sfmx_align_params* p, double* sums, int32_t* n);
+/* the Gauss-Newton loop from the given view: at most max_iters evaluations, each followed by a step unless it ends the loop.
+ * TOO_FEW and DEGENERATE return the last view whose evaluation gave a step (the input view if none did).  The statuses are
+ * results: the call returns SFMX_OK with them. */
+int sfmx_align_view(sfmx_ctx* ctx, sfmx_align* al, sfmx_fusion* fu, const sfmx_fusion_view* view, const int16_t* disp16, int on_device,
+                    const sfmx_align_params* p, sfmx_align_result* out);
+/* the loop for any volume, as sfmx_align_system_arrays */
+int sfmx_align_view_arrays(sfmx_ctx* ctx, sfmx_align* al, const sfmx_fusion_params* vol, const double* sum, const int32_t* count,
+                           int volume_on_device, const sfmx_fusion_view* view, const int16_t* disp16, int on_device,
+                           const sfmx_align_params* p, sfmx_align_result* out);
+/* the loop on the last map sfmx_stereo_disparity computed on st, read in place on the device */
+int sfmx_align_stereo_view(sfmx_ctx* ctx, sfmx_align* al, sfmx_fusion* fu, const sfmx_fusion_view* view, const sfmx_stereo* st,
+                           const sfmx_align_params* p, sfmx_align_result* out);
+/* device time (us) of the evaluations of the last call when timing is on (sfmx_set_timing), else 0 */
+double sfmx_align_last_us(const sfmx_align* al);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

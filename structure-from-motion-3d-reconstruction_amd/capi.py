@@ -50,6 +50,8 @@ SYMBOLS = [
     "sfmx_raycast_default_params", "sfmx_raycast_check_params", "sfmx_raycast_create", "sfmx_raycast_destroy", "sfmx_raycast_render",
     "sfmx_raycast_render_arrays", "sfmx_raycast_read", "sfmx_raycast_device_surface", "sfmx_raycast_shade", "sfmx_raycast_last_us",
     "sfmx_raycast_last_samples",
+    "sfmx_align_default_params", "sfmx_align_check_params", "sfmx_align_create", "sfmx_align_destroy", "sfmx_align_system",
+    "sfmx_align_system_arrays", "sfmx_align_view", "sfmx_align_view_arrays", "sfmx_align_stereo_view", "sfmx_align_last_us",
 ]
 
 
@@ -260,6 +262,54 @@ def raycast_check_params(**kw) -> bool:
     return load_library().sfmx_raycast_check_params(byref(raycast_params(**kw))) == SFMX_OK
 
 
+ALIGN_ITERS_CAP = 64  # SFMX_ALIGN_ITERS_CAP
+ALIGN_CONVERGED, ALIGN_MAX_ITERS, ALIGN_TOO_FEW, ALIGN_DEGENERATE = range(4)
+ALIGN_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")
+
+
+class AlignParams(ctypes.Structure):
+    _fields_ = [("max_iters", c_int), ("stride", c_int), ("disp_min", c_double), ("min_weight", c_int), ("min_pixels", c_int),
+                ("damping", c_double), ("eps_rot", c_double), ("eps_trans", c_double)]
+
+
+class AlignResult(ctypes.Structure):
+    _fields_ = [("view", FusionView), ("status", c_int), ("iterations", c_int), ("n", c_int32 * ALIGN_ITERS_CAP),
+                ("e", c_double * ALIGN_ITERS_CAP), ("rot", c_double * ALIGN_ITERS_CAP), ("trans", c_double * ALIGN_ITERS_CAP)]
+
+    def asdict(self) -> dict:
+        """dict(view=dict(R_rw, c_left, f, cx, cy, B, w, h), status, iterations, trace=[(n, e, |omega|, |v|), ...])"""
+        v = self.view
+        k = int(self.iterations)
+        return dict(view=dict(R_rw=np.array(v.R_rw[:]).reshape(3, 3), c_left=np.array(v.c_left[:]), f=v.f, cx=v.cx, cy=v.cy, B=v.B,
+                              w=int(v.w), h=int(v.h)),
+                    status=int(self.status), iterations=k,
+                    trace=[(int(self.n[i]), float(self.e[i]), float(self.rot[i]), float(self.trans[i])) for i in range(k)])
+
+
+ALIGN_DEFAULTS = dict(max_iters=10, stride=1, disp_min=1.0, min_weight=0, min_pixels=64, damping=0.0, eps_rot=1e-6, eps_trans=1e-4)
+
+
+def align_params(**kw) -> AlignParams:
+    unknown = set(kw) - set(ALIGN_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown align parameters {sorted(unknown)}")
+    d = {**ALIGN_DEFAULTS, **kw}
+    return AlignParams(int(d["max_iters"]), int(d["stride"]), float(d["disp_min"]), int(d["min_weight"]), int(d["min_pixels"]),
+                       float(d["damping"]), float(d["eps_rot"]), float(d["eps_trans"]))
+
+
+def align_default_params() -> dict:
+    """sfmx_align_default_params as a dict (needs no device)"""
+    p = AlignParams()
+    load_library().sfmx_align_default_params(byref(p))
+    return {k: getattr(p, k) for k, _ in AlignParams._fields_}
+
+
+def align_check_params(**kw) -> bool:
+    """True if the sfmx_align entries would accept the parameters; needs no device"""
+    return load_library().sfmx_align_check_params(byref(align_params(**kw))) == SFMX_OK
+
+
 def stereo_check_params(w: int, h: int, **kw) -> bool:
     """True if sfmx_stereo_create would accept (w, h, params); needs no device"""
     return load_library().sfmx_stereo_check_params(c_int(w), c_int(h), byref(stereo_params(**kw))) == SFMX_OK
@@ -295,6 +345,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_sdist_last_us.restype = c_double
         _lib.sfmx_raycast_last_us.restype = c_double
         _lib.sfmx_raycast_last_samples.restype = c_uint64
+        _lib.sfmx_align_last_us.restype = c_double
     return _lib
 
 
@@ -842,6 +893,95 @@ class Raycast:
             pass
 
 
+class Align:
+    """sfmx_align: registration of a view to a TSDF volume by direct Gauss-Newton alignment.  The device work
+    buffers grow on demand and are kept between calls."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_align_create(ctx.h_, byref(self.h_)))
+
+    def _volume(self, vol):
+        """(fusion handle or None, the arguments of the _arrays entries, what must stay alive)"""
+        if isinstance(vol, Fusion):
+            return vol.h_, None, None
+        sum_, count, origin, voxel = vol[:4]
+        on_dev = isinstance(sum_, int)
+        if on_dev != isinstance(count, int):
+            raise TypeError("sum and count: both host arrays or both device pointers")
+        if on_dev:
+            dims = vol[4]
+            ps, pc = c_void_p(sum_), c_void_p(count)
+        else:
+            sum_ = _f64(sum_)
+            count = np.ascontiguousarray(count, np.int32)
+            assert sum_.ndim == 3 and count.shape == sum_.shape
+            dims = sum_.shape[::-1]
+            ps, pc = sum_.ctypes.data_as(c_void_p), count.ctypes.data_as(c_void_p)
+        fp = fusion_params(origin, voxel, dims)
+        return None, (byref(fp), ps, pc, c_int(1 if on_dev else 0)), (fp, sum_, count)
+
+    @staticmethod
+    def _map(cam, disp16, shape):
+        if isinstance(disp16, int):
+            h, w = shape
+            return fusion_view(cam, w, h), c_void_p(disp16), 1, None
+        disp16 = np.ascontiguousarray(disp16, np.int16)
+        h, w = disp16.shape
+        return fusion_view(cam, w, h), disp16.ctypes.data_as(c_void_p), 0, disp16
+
+    def system(self, vol, cam: dict, disp16, shape=None, **params):
+        """one evaluation at cam's pose, no step: (sums f64 [28] = A row by row upper, b, e; n).  vol: a Fusion (its pending
+        views are integrated first), or (sum, count, origin, voxel) host arrays, or ints (device pointers) followed by dims.
+        cam: dict(R_rw, c_left, f, cx, cy, B); disp16: int16 [h][w] array, or an int (device pointer) with shape=(h, w).
+        params: ALIGN_DEFAULTS keys."""
+        p = align_params(**params)
+        fu, arr, keep = self._volume(vol)
+        v, pd, on_dev, keep2 = self._map(cam, disp16, shape)
+        sums, n = np.zeros(28), c_int32(0)
+        if fu is not None:
+            self.ctx._chk(self.ctx.lib.sfmx_align_system(self.ctx.h_, self.h_, fu, byref(v), pd, c_int(on_dev), byref(p), _p(sums, c_double),
+                                                         byref(n)))
+        else:
+            self.ctx._chk(self.ctx.lib.sfmx_align_system_arrays(self.ctx.h_, self.h_, *arr, byref(v), pd, c_int(on_dev), byref(p),
+                                                                _p(sums, c_double), byref(n)))
+        return sums, int(n.value)
+
+    def view(self, vol, cam: dict, disp16, shape=None, **params) -> dict:
+        """the Gauss-Newton loop from cam's pose: AlignResult.asdict().  disp16 may also be a Stereo: its last map is read in
+        place on the device (vol must then be a Fusion)."""
+        p = align_params(**params)
+        fu, arr, keep = self._volume(vol)
+        out = AlignResult()
+        if isinstance(disp16, Stereo):
+            if fu is None:
+                raise TypeError("a Stereo map needs a Fusion volume")
+            v = fusion_view(cam, disp16.w, disp16.h)
+            self.ctx._chk(self.ctx.lib.sfmx_align_stereo_view(self.ctx.h_, self.h_, fu, byref(v), disp16.h_, byref(p), byref(out)))
+            return out.asdict()
+        v, pd, on_dev, keep2 = self._map(cam, disp16, shape)
+        if fu is not None:
+            self.ctx._chk(self.ctx.lib.sfmx_align_view(self.ctx.h_, self.h_, fu, byref(v), pd, c_int(on_dev), byref(p), byref(out)))
+        else:
+            self.ctx._chk(self.ctx.lib.sfmx_align_view_arrays(self.ctx.h_, self.h_, *arr, byref(v), pd, c_int(on_dev), byref(p), byref(out)))
+        return out.asdict()
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_align_last_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_align_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Stereo:
     """Device buffers of sfmx_stereo for one (w, h, params); disparity() runs rectify -> census -> SGM -> select -> speckle."""
 
@@ -1184,6 +1324,9 @@ class Context:
 
     def raycast(self) -> "Raycast":
         return Raycast(self)
+
+    def align(self) -> "Align":
+        return Align(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

@@ -39,8 +39,6 @@ __device__ __forceinline__ double rc_coord(double c, double dw, double o, double
 
 __device__ __forceinline__ double rc_z(const RcMarch& m, int k) { return m.z_min + (double)k * m.step; }
 
-__device__ __forceinline__ double rc_lerp(double p, double q, double t) { return p + t * (q - p); }
-
 // sample k lies before (after) the run of samples inside the grid: on some axis its coordinate has not yet reached (has left)
 // the grid in the direction the ray moves.  By monotonicity this then holds for every smaller (larger) k as well.
 __device__ __forceinline__ bool rc_before(const double* c, const double* dw, const double* o, double inv, const double* top, double z) {
@@ -141,9 +139,7 @@ __global__ __launch_bounds__(256) void k_rc_render(const double* __restrict__ su
       ok = cell_ok;
       if (ok) {
         const double fx = g0 - (double)i, fy = g1 - (double)j, fz = g2 - (double)kk;
-        const double c00 = rc_lerp(s[0], s[1], fx), c10 = rc_lerp(s[2], s[3], fx);
-        const double c01 = rc_lerp(s[4], s[5], fx), c11 = rc_lerp(s[6], s[7], fx);
-        cur = rc_lerp(rc_lerp(c00, c10, fy), rc_lerp(c01, c11, fy), fz);
+        cur = fu_trilerp(s, fx, fy, fz);
         if (prev_ok && prev > 0.0 && cur <= 0.0) {
           hit = true;
           kh = k;
@@ -178,28 +174,7 @@ __global__ __launch_bounds__(256) void k_rc_render(const double* __restrict__ su
       for (int b = 0; b < 8; b++) ok &= cnt[L + (b & 1) + ((b >> 1) & 1) * sy + ((b >> 2) & 1) * sz] >= g.minw;
       if (ok) {
         const double fx = gp[0] - (double)i, fy = gp[1] - (double)j, fz = gp[2] - (double)kk;
-        double cy[2][3];  // after the lerps along x and y, per z
-#pragma unroll
-        for (int bz = 0; bz < 2; bz++) {
-          double cx[2][3];
-#pragma unroll
-          for (int by = 0; by < 2; by++) {
-            double G[2][3];
-#pragma unroll
-            for (int bx = 0; bx < 2; bx++) {
-              const size_t Lq = L + bx + by * sy + bz * sz;
-              double sq;
-              (void)fu_value(sum, cnt, Lq, g.minw, sq);
-              fu_grad(sum, cnt, g, i + bx, j + by, kk + bz, Lq, sq, G[bx][0], G[bx][1], G[bx][2]);
-            }
-#pragma unroll
-            for (int a = 0; a < 3; a++) cx[by][a] = rc_lerp(G[0][a], G[1][a], fx);
-          }
-#pragma unroll
-          for (int a = 0; a < 3; a++) cy[bz][a] = rc_lerp(cx[0][a], cx[1][a], fy);
-        }
-#pragma unroll
-        for (int a = 0; a < 3; a++) N[a] = rc_lerp(cy[0][a], cy[1][a], fz);
+        fu_grad_trilerp(sum, cnt, g, i, j, kk, L, fx, fy, fz, N);
       }
     }
     const double len = sqrt((N[0] * N[0] + N[1] * N[1]) + N[2] * N[2]);

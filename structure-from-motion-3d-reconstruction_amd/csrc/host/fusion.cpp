@@ -64,6 +64,10 @@
 #pragma weak sfmx_raycast_render
 #pragma weak sfmx_raycast_read
 #pragma weak sfmx_raycast_shade
+#pragma weak sfmx_align_check_params
+#pragma weak sfmx_align_create
+#pragma weak sfmx_align_destroy
+#pragma weak sfmx_align_stereo_view
 
 namespace {
 
@@ -76,7 +80,9 @@ struct Guard {
   sfmx_clean* cl = nullptr;
   sfmx_sdist* sd = nullptr;
   sfmx_raycast* rc = nullptr;
+  sfmx_align* al = nullptr;
   ~Guard() {
+    if (al) sfmx_align_destroy(ctx, al);
     if (rc) sfmx_raycast_destroy(ctx, rc);
     if (sd) sfmx_sdist_destroy(ctx, sd);
     if (cl) sfmx_clean_destroy(ctx, cl);
@@ -285,6 +291,16 @@ int sfmx_host_fusion_mesh_rc(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
                              sfmx_surface_eval_result* ev, const sfmx_render_request* render, sfmx_fusion_result_ex* res,
                              const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_al(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts, gt,
+                                  ev, render, nullptr, res, ply_path, warn, warn_cap);
+}
+
+int sfmx_host_fusion_mesh_al(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -298,6 +314,7 @@ int sfmx_host_fusion_mesh_rc(sfmx_ctx* ctx, const uint8_t* const* images, int on
   if (render && (!&sfmx_raycast_check_params || !&sfmx_raycast_create || !&sfmx_raycast_destroy || !&sfmx_raycast_render ||
                  !&sfmx_raycast_read || !&sfmx_raycast_shade))
     return SFMX_ERR_UNSUPPORTED;
+  if (align && (!&sfmx_align_check_params || !&sfmx_align_create || !&sfmx_align_destroy || !&sfmx_align_stereo_view)) return SFMX_ERR_UNSUPPORTED;
   int rc = sfmx_stereo_check_params(w, h, sp);
   if (rc != SFMX_OK) return rc;
   rc = sfmx_fusion_check_params(fp);
@@ -335,10 +352,24 @@ int sfmx_host_fusion_mesh_rc(sfmx_ctx* ctx, const uint8_t* const* images, int on
     if (rc != SFMX_OK) return rc;
     for (int q = 0; q < render->n_cameras; q++) render->out[q].hits = 0;
   }
+  if (align) {
+    // the filter needs every pose before anything is integrated
+    if (cs || align->seed < 1 || (m > 0 && !align->out)) return SFMX_ERR_INVALID;
+    rc = sfmx_align_check_params(&align->params);
+    if (rc != SFMX_OK) return rc;
+    for (int q = 0; q < m; q++) {
+      align->out[q] = sfmx_align_result{};
+      align->out[q].status = -1;
+    }
+  }
   std::string log;
   Guard g{ctx};
   rc = sfmx_fusion_create(ctx, fp, &g.fu);
   if (rc != SFMX_OK) return rc;
+  if (align) {
+    rc = sfmx_align_create(ctx, &g.al);
+    if (rc != SFMX_OK) return rc;
+  }
   if (cs) {
     rc = sfmx_consist_create(ctx, &g.cs);
     if (rc != SFMX_OK) return rc;
@@ -383,6 +414,17 @@ int sfmx_host_fusion_mesh_rc(sfmx_ctx* ctx, const uint8_t* const* images, int on
     v.B = r.B;
     v.w = w;
     v.h = h;
+    if (align && res->n_views >= align->seed) {
+      // against the volume integrated so far (the call integrates what is pending); the refined view enters it
+      sfmx_align_result& ar = align->out[q];
+      rc = sfmx_align_stereo_view(ctx, g.al, g.fu, &v, g.st, &align->params, &ar);
+      if (rc != SFMX_OK) return rc;
+      if (ar.status == SFMX_ALIGN_TOO_FEW || ar.status == SFMX_ALIGN_DEGENERATE)
+        log += "WARN: fusion pair " + tag + " not aligned (" + (ar.status == SFMX_ALIGN_TOO_FEW ? "too few samples" : "degenerate system") +
+               "), given view kept\n";
+      else
+        v = ar.view;
+    }
     // with cs the view waits in the consist object: its filtered map is queued after the loop
     rc = cs ? sfmx_consist_add_stereo_view(ctx, g.cs, &v, g.st) : sfmx_fusion_add_stereo_view(ctx, g.fu, &v, g.st);
     if (rc != SFMX_OK) return rc;

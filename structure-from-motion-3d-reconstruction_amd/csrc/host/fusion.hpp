@@ -127,4 +127,24 @@ int sfmx_host_fusion_mesh_rc(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
                              sfmx_surface_eval_result* ev, const sfmx_render_request* render, sfmx_fusion_result_ex* res,
                              const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_rc with each later pair's view registered to the volume before it enters it.  align =
+// NULL: exactly sfmx_host_fusion_mesh_rc.  Otherwise the pairs are processed in list order: the first `seed` (>= 1) integrated
+// pairs (skipped ones do not count) enter at their given views; each later pair's view is aligned against the volume integrated
+// so far (sfmx_align_stereo_view, which integrates what is pending) with params, and it is the refined view that is queued into
+// the volume and, with app, retained as the shade view.  out[q] (caller allocated, [m]) is the result of listed pair q; its
+// status is -1 for a pair that was not aligned (a seed pair or a skipped one).  On SFMX_ALIGN_TOO_FEW or _DEGENERATE the pair
+// keeps its given view and one WARN line says so.  align together with cs is refused with SFMX_ERR_INVALID: the filter needs
+// every pose before anything is integrated.
+struct sfmx_align_request {
+  int seed;
+  sfmx_align_params params;
+  sfmx_align_result* out;  // [m]
+};
+int sfmx_host_fusion_mesh_al(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
 }

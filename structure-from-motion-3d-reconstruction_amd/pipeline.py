@@ -211,6 +211,13 @@ class RenderRequest(ctypes.Structure):
     _fields_ = [("cameras", POINTER(capi.FusionView)), ("n_cameras", c_int), ("params", capi.RaycastParams), ("out", POINTER(RenderOut))]
 
 
+ALIGN_KEYS = ("seed", "max_iters", "stride", "min_pixels", "damping", "eps_rot", "eps_trans", "min_weight")
+
+
+class AlignRequest(ctypes.Structure):
+    _fields_ = [("seed", c_int), ("params", capi.AlignParams), ("out", POINTER(capi.AlignResult))]
+
+
 def write_pgm(path: str, image) -> None:
     """a u8 [h][w] image as a binary PGM (P5)"""
     image = np.ascontiguousarray(image, np.uint8)
@@ -263,7 +270,7 @@ def _split_fusion_params(params: dict):
 
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
-         consistency=False, clean=False, evaluate=None, render=None, **params) -> dict:
+         consistency=False, clean=False, evaluate=None, render=None, align=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -286,7 +293,13 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     pgm_prefix=None) -- the integrated volume is ray cast from each camera at w x h (z_min and z_max are required):
     the dict gains renders = [dict(depth, normals, points, shaded, hits), ...]; with appearance each also carries grey and
     pixel_views, the shade stage over the render's points and normals from the retained views.  pgm_prefix writes
-    <prefix>_<i>_shaded.pgm (and _grey.pgm with appearance).  The mesh and the PLY are what they are without render."""
+    <prefix>_<i>_shaded.pgm (and _grey.pgm with appearance).  The mesh and the PLY are what they are without render.
+    align: True, or dict(seed=1, max_iters=, stride=, min_pixels=, damping=, eps_rot=, eps_trans=, min_weight=) (disp_min is the
+    fusion's) -- the pairs are processed in list order: the first `seed` integrated pairs enter the volume at their given poses,
+    every later pair's view is first registered to the volume integrated so far and enters it, and the shade views
+    of appearance, at its refined view.  The dict gains alignment = [dict(pair, status, iterations, n, rms, view), ...], one per
+    aligned pair: status as capi.ALIGN_STATUS, n and rms = sqrt(e / n) of the last evaluation, view the refined camera.  A pair
+    whose alignment ends TOO_FEW or DEGENERATE keeps its given view (one WARN line).  Not together with consistency."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -367,12 +380,28 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             for a in rarr])
         rq = RenderRequest(rviews, len(rcams), capi.raycast_params(rkw["z_min"], rkw["z_max"], rkw.get("step", 0.0), rkw.get("min_weight", 0),
                                                                    rkw.get("background", 0)), routs)
-    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None:
+    aq = None
+    if align:
+        gkw = {} if align is True else dict(align)
+        unknown = set(gkw) - set(ALIGN_KEYS)
+        if unknown:
+            raise TypeError(f"unknown align parameters {sorted(unknown)}")
+        seed = int(gkw.pop("seed", 1))
+        aouts = (capi.AlignResult * max(len(pr), 1))()
+        aq = AlignRequest(seed, capi.align_params(disp_min=fp.disp_min, **gkw), aouts)
+    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if rq is not None:
+        if aq is not None:
+            rc = lib.sfmx_host_fusion_mesh_al(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None,
+                                              byref(rq) if rq is not None else None, byref(aq), *tail)
+        elif rq is not None:
             rc = lib.sfmx_host_fusion_mesh_rc(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -418,6 +447,15 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                     write_pgm(f"{rkw['pgm_prefix']}_{i}_shaded.pgm", a["shaded"])
                     if ap is not None:
                         write_pgm(f"{rkw['pgm_prefix']}_{i}_grey.pgm", a["grey"])
+        if aq is not None:
+            out["alignment"] = []
+            for q in range(len(pr)):
+                if aouts[q].status < 0:
+                    continue
+                r = aouts[q].asdict()
+                n_last, e_last = r["trace"][-1][0], r["trace"][-1][1]
+                out["alignment"].append(dict(pair=(int(pr[q, 0]), int(pr[q, 1])), status=r["status"], iterations=r["iterations"], n=n_last,
+                                             rms=float(np.sqrt(e_last / n_last)) if n_last > 0 else float("nan"), view=r["view"]))
         return out
     res = FusionResult()
     rc = lib.sfmx_host_fusion_mesh(ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp),
@@ -471,7 +509,8 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     gains templeRing_mesh_fused.ply; 'appearance' (True or a dict, as fuse) adds normals and vertex grey to both;
     'consistency' (True or a dict, as fuse) filters the pairs' disparity maps against each other first; 'clean' (True or a
     dict, as fuse) removes the surface's small connected components; 'evaluate' (a dict, as fuse) evaluates the final mesh against
-    a ground-truth mesh; 'render' (a dict, as fuse) ray casts the volume from further cameras.  The run itself, its log and every other output are unchanged.
+    a ground-truth mesh; 'render' (a dict, as fuse) ray casts the volume from further cameras; 'align' (True or a dict, as fuse) registers each later
+    pair's view to the volume before it enters it.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -537,8 +576,9 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         clean = fz.pop("clean", False)
         evaluate = fz.pop("evaluate", None)
         render = fz.pop("render", None)
+        align = fz.pop("align", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
-                                 appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, **fz)
+                                 appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align, **fz)
     return out
 
 

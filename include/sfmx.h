@@ -619,6 +619,62 @@ int sfmx_align_stereo_view(sfmx_ctx* ctx, sfmx_align* al, sfmx_fusion* fu, const
 /* device time (us) of the evaluations of the last call when timing is on (sfmx_set_timing), else 0 */
 double sfmx_align_last_us(const sfmx_align* al);
 
+/* ---- simplifying a triangle mesh: exact vertex clustering on a uniform grid --------------------------------- */
+/* Per vertex and component q = (x - origin) / cell, c = floor(q), t = q - c and Q = (int64)floor(t 2^30 + 0.5), in this order in
+ * IEEE double without contraction.  A cluster is an occupied cell; clusters are numbered in ascending linear index
+ * (cx - cmin0) + dims0 ((cy - cmin1) + dims1 (cz - cmin2)) over the box of the occupied cells.  Every input vertex contributes to
+ * its cluster: S = sum Q (int64) and cnt per cluster, position = origin + ((double)c + ((double)S / (double)cnt) / 2^30) cell.
+ * With normals, Qn = (int64)floor(n 2^30 + 0.5), s = (double)sum Qn, len = sqrt((s0 s0 + s1 s1) + s2 s2), normal = s / len or 0
+ * when len == 0.  A face becomes the triple of its corners' clusters: dropped as degenerate when two are equal, else rotated
+ * (never reflected) so that its smallest cluster comes first; of the faces with the same triple only the one with the smallest
+ * input index is kept (the others are duplicates; the reversed triple is another triple).  Kept faces stay in input order,
+ * output vertices are the clusters a kept face uses in ascending cluster number, face indices are renumbered.  The sums are
+ * integers, so every output is bit-identical to the NumPy restatement in tests/simplify_ref.py whatever the schedule. */
+typedef struct sfmx_simplify sfmx_simplify;  /* device work buffers and the last result; they grow on demand and are kept */
+typedef struct sfmx_simplify_params {
+  double cell;       /* edge of a grid cell; finite, > 0; no default (a length in the caller's units) */
+  double origin[3];  /* a corner of the grid; finite (default 0) */
+} sfmx_simplify_params;
+void sfmx_simplify_default_params(sfmx_simplify_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_simplify_check_params(const sfmx_simplify_params* p);
+int sfmx_simplify_create(sfmx_ctx* ctx, sfmx_simplify** out);
+void sfmx_simplify_destroy(sfmx_ctx* ctx, sfmx_simplify* sp);
+/* verts double [n][3], normals double [n][3] or NULL, faces int32 [m][3]; host pointers or (on_device = 1) device pointers,
+ * 0 <= n, m < 2^30.  SFMX_ERR_INVALID (found on the device, nothing is accessed through a bad index; the object stays usable
+ * and no result is left) for a coordinate that is not finite or whose cell index exceeds 2^30 in magnitude, a normal component
+ * that is not finite or exceeds 4 in magnitude, a face index outside [0, n), and a box of occupied cells of more than 2^27
+ * cells.  The two counts (output vertices and faces) may each be NULL. */
+int sfmx_simplify_run(sfmx_ctx* ctx, sfmx_simplify* sp, const double* verts, const double* normals, int n, const int32_t* faces, int m,
+                      int on_device, const sfmx_simplify_params* p, int* n_verts_out, int* n_faces_out);
+/* the same for the surface the last sfmx_fusion_extract / _extract_normals with arrays left on the device inside fu, with its
+ * normals when that call made them, and for the cleaned surface (and normals) of the last successful run on cl; no host round
+ * trip.  SFMX_ERR_INVALID when there is none. */
+int sfmx_simplify_fusion(sfmx_ctx* ctx, sfmx_simplify* sp, const sfmx_fusion* fu, const sfmx_simplify_params* p, int* n_verts_out,
+                         int* n_faces_out);
+int sfmx_simplify_clean(sfmx_ctx* ctx, sfmx_simplify* sp, const sfmx_clean* cl, const sfmx_simplify_params* p, int* n_verts_out,
+                        int* n_faces_out);
+/* the last successful run to the host: verts_out / normals_out double [n'][3], faces_out int32 [m'][3] (canonical form),
+ * vert_dst int32 [n] (the output vertex of each INPUT vertex, or -1), face_src int32 [m'] (the input index of each output
+ * face), members int32 [n'] (input vertices per output vertex); any may be NULL (normals_out is left alone when the run had no
+ * normals).  SFMX_ERR_INVALID before a successful run; a call that fails for any reason (parameters included) leaves no result. */
+int sfmx_simplify_read(sfmx_ctx* ctx, sfmx_simplify* sp, double* verts_out, double* normals_out, int32_t* faces_out, int32_t* vert_dst,
+                       int32_t* face_src, int32_t* members);
+/* the sizes sfmx_simplify_read copies by: input vertices and faces (n, m) and output vertices and faces (n', m') of the last
+ * successful run; any pointer may be NULL.  SFMX_ERR_INVALID (and zeros) before a successful run; needs no context. */
+int sfmx_simplify_sizes(const sfmx_simplify* sp, int* n, int* m, int* n_verts_out, int* n_faces_out);
+/* of the last successful run: clusters (occupied cells), degenerate and duplicate faces (m = degenerate + duplicates + m'), n'
+ * and m'; any pointer may be NULL.  SFMX_ERR_INVALID (and zeros) before a successful run; needs no context. */
+int sfmx_simplify_counts(const sfmx_simplify* sp, int* clusters, int* degenerate, int* duplicates, int* n_verts_out, int* n_faces_out);
+/* the output vertices and normals of the last successful run on the device (for sfmx_shade_vertices with on_device = 1);
+ * *normals is NULL when the run had none.  Returns n', or -1 before a successful run.  Valid until the next run on sp. */
+int sfmx_simplify_device_surface(const sfmx_simplify* sp, const double** verts, const double** normals);
+/* the output vertices and faces on the device and *n_faces = m' (for sfmx_sdist_set_target / _query with on_device = 1); any
+ * pointer may be NULL.  Returns n', or -1 before a successful run.  Valid until the next run on sp. */
+int sfmx_simplify_device_mesh(const sfmx_simplify* sp, const double** verts, const int32_t** faces, int* n_faces);
+/* device time (us) from the first to the last launch of the last run when timing is on (sfmx_set_timing), else 0 */
+double sfmx_simplify_last_us(const sfmx_simplify* sp);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

@@ -52,6 +52,9 @@ SYMBOLS = [
     "sfmx_raycast_last_samples",
     "sfmx_align_default_params", "sfmx_align_check_params", "sfmx_align_create", "sfmx_align_destroy", "sfmx_align_system",
     "sfmx_align_system_arrays", "sfmx_align_view", "sfmx_align_view_arrays", "sfmx_align_stereo_view", "sfmx_align_last_us",
+    "sfmx_simplify_default_params", "sfmx_simplify_check_params", "sfmx_simplify_create", "sfmx_simplify_destroy", "sfmx_simplify_run",
+    "sfmx_simplify_fusion", "sfmx_simplify_clean", "sfmx_simplify_read", "sfmx_simplify_sizes", "sfmx_simplify_counts",
+    "sfmx_simplify_device_surface", "sfmx_simplify_device_mesh", "sfmx_simplify_last_us",
 ]
 
 
@@ -212,6 +215,37 @@ def clean_check_params(**kw) -> bool:
     return load_library().sfmx_clean_check_params(byref(clean_params(**kw))) == SFMX_OK
 
 
+class SimplifyParams(ctypes.Structure):
+    _fields_ = [("cell", c_double), ("origin", c_double * 3)]
+
+
+# cell has no default (a length in the caller's units)
+SIMPLIFY_DEFAULTS = dict(origin=(0.0, 0.0, 0.0))
+
+
+def simplify_params(cell=0.0, **kw) -> SimplifyParams:
+    unknown = set(kw) - set(SIMPLIFY_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown simplify parameters {sorted(unknown)}")
+    kw = {**SIMPLIFY_DEFAULTS, **kw}
+    p = SimplifyParams()
+    p.cell = float(cell)
+    p.origin[:] = [float(v) for v in kw["origin"]]
+    return p
+
+
+def simplify_default_params() -> dict:
+    """sfmx_simplify_default_params as a dict (needs no device)"""
+    p = SimplifyParams()
+    load_library().sfmx_simplify_default_params(byref(p))
+    return dict(cell=p.cell, origin=tuple(p.origin))
+
+
+def simplify_check_params(cell=0.0, **kw) -> bool:
+    """True if sfmx_simplify_run / _fusion / _clean would accept the parameters; needs no device"""
+    return load_library().sfmx_simplify_check_params(byref(simplify_params(cell, **kw))) == SFMX_OK
+
+
 class SdistParams(ctypes.Structure):
     _fields_ = [("d_max", c_double), ("cell", c_double)]
 
@@ -346,6 +380,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_raycast_last_us.restype = c_double
         _lib.sfmx_raycast_last_samples.restype = c_uint64
         _lib.sfmx_align_last_us.restype = c_double
+        _lib.sfmx_simplify_last_us.restype = c_double
     return _lib
 
 
@@ -706,6 +741,106 @@ class Clean:
     def close(self):
         if self.h_:
             self.ctx.lib.sfmx_clean_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Simplify:
+    """sfmx_simplify: exact vertex clustering of a triangle mesh on a uniform grid; the work buffers are kept
+    between calls."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_simplify_create(ctx.h_, byref(self.h_)))
+
+    def run(self, verts, faces, normals=None, n=None, m=None, cell=0.0, **params):
+        """verts / normals float64 [n][3] and faces int32 [m][3]: numpy arrays, or ints (device pointers) with n and m given;
+        normals may be None.  cell is required; params: SIMPLIFY_DEFAULTS keys.  Returns counts()."""
+        p = simplify_params(cell, **params)
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int) or (normals is not None and on_dev != isinstance(normals, int)):
+            raise TypeError("verts, normals and faces: all host arrays or all device pointers")
+        if on_dev:
+            pv, pf, pn = c_void_p(verts), c_void_p(faces), (c_void_p(normals) if normals is not None else None)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            n, m = len(verts), len(faces)
+            normals = None if normals is None else _f64(normals).reshape(-1, 3)
+            assert normals is None or len(normals) == n
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+            pn = normals.ctypes.data_as(c_void_p) if normals is not None else None
+        self.ctx._chk(self.ctx.lib.sfmx_simplify_run(self.ctx.h_, self.h_, pv, pn, c_int(n), pf, c_int(m), c_int(1 if on_dev else 0),
+                                                     byref(p), None, None))
+        return self.counts()
+
+    def fusion(self, fu: "Fusion", cell=0.0, **params):
+        """the surface fu.extract() / fu.extract_normals() left on the device; returns counts()"""
+        p = simplify_params(cell, **params)
+        self.ctx._chk(self.ctx.lib.sfmx_simplify_fusion(self.ctx.h_, self.h_, fu.h_, byref(p), None, None))
+        return self.counts()
+
+    def clean(self, cl: "Clean", cell=0.0, **params):
+        """the cleaned surface of cl's last run, on the device; returns counts()"""
+        p = simplify_params(cell, **params)
+        self.ctx._chk(self.ctx.lib.sfmx_simplify_clean(self.ctx.h_, self.h_, cl.h_, byref(p), None, None))
+        return self.counts()
+
+    def sizes(self):
+        """(n, m, n', m') of the last successful run: input and output vertices and faces; raises before one"""
+        s = [c_int(0) for _ in range(4)]
+        rc = self.ctx.lib.sfmx_simplify_sizes(self.h_, *[byref(x) for x in s])
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_simplify_sizes: no successful run")
+        return tuple(x.value for x in s)
+
+    def counts(self) -> dict:
+        """dict(clusters, degenerate, duplicates, n_verts, n_faces) of the last successful run; raises before one"""
+        s = [c_int(0) for _ in range(5)]
+        rc = self.ctx.lib.sfmx_simplify_counts(self.h_, *[byref(x) for x in s])
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_simplify_counts: no successful run")
+        return dict(zip(("clusters", "degenerate", "duplicates", "n_verts", "n_faces"), (x.value for x in s)))
+
+    def read(self, normals: bool = False):
+        """the last run: dict(verts f64 [n'][3], faces i32 [m'][3], vert_dst i32 [n], face_src i32 [m'], members i32 [n']), plus
+        normals f64 [n'][3] when asked for (the run must have had them).  The arrays are sized by what the library says it will
+        copy."""
+        n, _, nv, nf = self.sizes()
+        verts, nrm, faces = np.zeros((max(nv, 1), 3)), np.zeros((max(nv, 1), 3)), np.zeros((max(nf, 1), 3), np.int32)
+        vdst, fsrc, mem = np.zeros(max(n, 1), np.int32), np.zeros(max(nf, 1), np.int32), np.zeros(max(nv, 1), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_simplify_read(self.ctx.h_, self.h_, _p(verts, c_double), _p(nrm, c_double) if normals else None,
+                                                      _p(faces, c_int32), _p(vdst, c_int32), _p(fsrc, c_int32), _p(mem, c_int32)))
+        out = dict(verts=verts[:nv].copy(), faces=faces[:nf].copy(), vert_dst=vdst[:n].copy(), face_src=fsrc[:nf].copy(),
+                   members=mem[:nv].copy())
+        if normals:
+            out["normals"] = nrm[:nv].copy()
+        return out
+
+    def device_surface(self):
+        """(n', device pointer of the output vertices, of the output normals or None); n' = -1 before a successful run"""
+        v, nr = c_void_p(), c_void_p()
+        n = int(self.ctx.lib.sfmx_simplify_device_surface(self.h_, byref(v), byref(nr)))
+        return n, v.value, nr.value
+
+    def device_mesh(self):
+        """(n', device pointer of the output vertices, of the output faces, m'); n' = -1 before a successful run"""
+        v, f, m = c_void_p(), c_void_p(), c_int(0)
+        n = int(self.ctx.lib.sfmx_simplify_device_mesh(self.h_, byref(v), byref(f), byref(m)))
+        return n, v.value, f.value, int(m.value)
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_simplify_last_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_simplify_destroy(self.ctx.h_, self.h_)
             self.h_ = c_void_p()
 
     def __del__(self):
@@ -1318,6 +1453,9 @@ class Context:
 
     def clean(self) -> "Clean":
         return Clean(self)
+
+    def simplify(self) -> "Simplify":
+        return Simplify(self)
 
     def sdist(self) -> "Sdist":
         return Sdist(self)

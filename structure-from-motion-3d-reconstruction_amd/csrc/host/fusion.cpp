@@ -68,6 +68,15 @@
 #pragma weak sfmx_align_create
 #pragma weak sfmx_align_destroy
 #pragma weak sfmx_align_stereo_view
+#pragma weak sfmx_simplify_check_params
+#pragma weak sfmx_simplify_create
+#pragma weak sfmx_simplify_destroy
+#pragma weak sfmx_simplify_fusion
+#pragma weak sfmx_simplify_clean
+#pragma weak sfmx_simplify_read
+#pragma weak sfmx_simplify_counts
+#pragma weak sfmx_simplify_device_surface
+#pragma weak sfmx_simplify_device_mesh
 
 namespace {
 
@@ -81,7 +90,9 @@ struct Guard {
   sfmx_sdist* sd = nullptr;
   sfmx_raycast* rc = nullptr;
   sfmx_align* al = nullptr;
+  sfmx_simplify* sm = nullptr;
   ~Guard() {
+    if (sm) sfmx_simplify_destroy(ctx, sm);
     if (al) sfmx_align_destroy(ctx, al);
     if (rc) sfmx_raycast_destroy(ctx, rc);
     if (sd) sfmx_sdist_destroy(ctx, sd);
@@ -301,6 +312,17 @@ int sfmx_host_fusion_mesh_al(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
                              sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
                              sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_sp(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts, gt,
+                                  ev, render, align, nullptr, nullptr, res, ply_path, warn, warn_cap);
+}
+
+int sfmx_host_fusion_mesh_sp(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, sfmx_fusion_result_ex* res,
+                             const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -315,6 +337,10 @@ int sfmx_host_fusion_mesh_al(sfmx_ctx* ctx, const uint8_t* const* images, int on
                  !&sfmx_raycast_read || !&sfmx_raycast_shade))
     return SFMX_ERR_UNSUPPORTED;
   if (align && (!&sfmx_align_check_params || !&sfmx_align_create || !&sfmx_align_destroy || !&sfmx_align_stereo_view)) return SFMX_ERR_UNSUPPORTED;
+  if (simplify && (!&sfmx_simplify_check_params || !&sfmx_simplify_create || !&sfmx_simplify_destroy || !&sfmx_simplify_fusion ||
+                   !&sfmx_simplify_clean || !&sfmx_simplify_read || !&sfmx_simplify_counts || !&sfmx_simplify_device_surface ||
+                   !&sfmx_simplify_device_mesh || !&sfmx_shade_vertices || !sdist_linked()))
+    return SFMX_ERR_UNSUPPORTED;
   int rc = sfmx_stereo_check_params(w, h, sp);
   if (rc != SFMX_OK) return rc;
   rc = sfmx_fusion_check_params(fp);
@@ -345,6 +371,12 @@ int sfmx_host_fusion_mesh_al(sfmx_ctx* ctx, const uint8_t* const* images, int on
     if (rc != SFMX_OK) return rc;
     if (clean_counts)
       for (int q = 0; q < 4; q++) clean_counts[q] = 0;
+  }
+  if (simplify) {
+    rc = sfmx_simplify_check_params(simplify);
+    if (rc != SFMX_OK) return rc;
+    if (simplify_counts)
+      for (int q = 0; q < 5; q++) simplify_counts[q] = 0;
   }
   if (render) {
     if (render->n_cameras < 0 || (render->n_cameras > 0 && (!render->cameras || !render->out))) return SFMX_ERR_INVALID;
@@ -476,6 +508,30 @@ int sfmx_host_fusion_mesh_al(sfmx_ctx* ctx, const uint8_t* const* images, int on
       clean_counts[3] = nf0 - nf;
     }
   }
+  if (simplify && nf > 0) {
+    // the cleaned surface lies inside the clean object; an uncleaned one is extracted with its arrays so that it lies inside
+    // the volume object (the extraction always returns them to the host as well)
+    const int nv0 = nv, nf0 = nf;
+    if (!clean) {
+      std::vector<double> tv((size_t)nv * 3), tn(app ? (size_t)nv * 3 : 0);
+      std::vector<int32_t> tf((size_t)nf * 3);
+      rc = app ? sfmx_fusion_extract_normals(ctx, g.fu, tv.data(), nv, tf.data(), nf, tn.data(), &nv, &nf)
+               : sfmx_fusion_extract(ctx, g.fu, tv.data(), nv, tf.data(), nf, &nv, &nf);
+      if (rc != SFMX_OK) return rc;
+    }
+    rc = sfmx_simplify_create(ctx, &g.sm);
+    if (rc == SFMX_OK)
+      rc = clean ? sfmx_simplify_clean(ctx, g.sm, g.cl, simplify, &nv, &nf) : sfmx_simplify_fusion(ctx, g.sm, g.fu, simplify, &nv, &nf);
+    int counts[3] = {};
+    if (rc == SFMX_OK) rc = sfmx_simplify_counts(g.sm, &counts[0], &counts[1], &counts[2], nullptr, nullptr);
+    if (rc != SFMX_OK) return rc;
+    if (simplify_counts) {
+      for (int q = 0; q < 3; q++) simplify_counts[q] = counts[q];
+      simplify_counts[3] = nv0;
+      simplify_counts[4] = nf0;
+    }
+  }
+  const bool simplified = g.sm != nullptr;
   if (nf > 0) {
     res->verts = static_cast<double*>(std::malloc((size_t)nv * 3 * sizeof(double)));
     res->faces = static_cast<int32_t*>(std::malloc((size_t)nf * 3 * sizeof(int32_t)));
@@ -490,7 +546,14 @@ int sfmx_host_fusion_mesh_al(sfmx_ctx* ctx, const uint8_t* const* images, int on
       res->n_views = keep;
       return SFMX_ERR_INVALID;
     }
-    if (clean) {
+    if (simplified) {
+      rc = sfmx_simplify_read(ctx, g.sm, res->verts, res->normals, res->faces, nullptr, nullptr, nullptr);
+      if (rc == SFMX_OK && app) {  // the simplified vertices are shaded with their own normals
+        const double *dv = nullptr, *dn = nullptr;
+        rc = sfmx_simplify_device_surface(g.sm, &dv, &dn) == nv && dn ? SFMX_OK : SFMX_ERR_INVALID;
+        if (rc == SFMX_OK) rc = sfmx_shade_vertices(ctx, g.sh, dv, dn, nv, 1, &ap, res->grey, res->views);
+      }
+    } else if (clean) {
       rc = sfmx_clean_read(ctx, g.cl, res->verts, res->normals, res->faces, nullptr, nullptr, nullptr, nullptr);
       if (rc == SFMX_OK && app) {  // per vertex: the uncleaned shading gathered by vert_src
         const double *dv = nullptr, *dn = nullptr;
@@ -513,19 +576,25 @@ int sfmx_host_fusion_mesh_al(sfmx_ctx* ctx, const uint8_t* const* images, int on
     res->n_faces = nf;
   }
   if (gt) {
-    // the final mesh is still on the device (inside the clean object, or inside the volume after the last extraction): it is
-    // the query set of the accuracy and the target of the completeness, with no host round trip
+    // the final mesh is still on the device (inside the simplify or the clean object, or inside the volume after the last
+    // extraction): it is the query set of the accuracy and the target of the completeness, with no host round trip
+    const double* mv = nullptr;
+    const int32_t* mf = nullptr;
+    int mnf = 0;
     const sfmx_sdist_params dp{gt->params.d_max, gt->params.cell};
     const std::vector<double> gq = compact(gt->verts, gt_used);
     std::vector<uint8_t> used;
     std::vector<double> d2((size_t)(nf > 0 ? nv : 0));
     rc = sfmx_sdist_create(ctx, &g.sd);
+    if (rc == SFMX_OK && simplified && nf > 0 && (sfmx_simplify_device_mesh(g.sm, &mv, &mf, &mnf) != nv || mnf != nf))
+      rc = SFMX_ERR_INVALID;
     if (rc == SFMX_OK) rc = sfmx_sdist_set_target(ctx, g.sd, gt->verts, gt->n_verts, gt->faces, gt->n_faces, 0, &dp);
     if (rc == SFMX_OK && nf > 0) {
       rc = used_mask(res->faces, nf, nv, used) ? SFMX_OK : SFMX_ERR_INVALID;
       if (rc == SFMX_OK)
-        rc = clean ? sfmx_sdist_query_clean(ctx, g.sd, g.cl, nv, d2.data(), nullptr, nullptr)
-                   : sfmx_sdist_query_fusion(ctx, g.sd, g.fu, nv, d2.data(), nullptr, nullptr);
+        rc = simplified ? sfmx_sdist_query(ctx, g.sd, mv, nv, 1, d2.data(), nullptr)
+             : clean    ? sfmx_sdist_query_clean(ctx, g.sd, g.cl, nv, d2.data(), nullptr, nullptr)
+                        : sfmx_sdist_query_fusion(ctx, g.sd, g.fu, nv, d2.data(), nullptr, nullptr);
     }
     if (rc == SFMX_OK) {
       eval_side(d2, &used, gt->params, &ev->n_rec, &ev->acc_within, &ev->accuracy, &ev->acc_mean, &ev->acc_max);
@@ -533,7 +602,9 @@ int sfmx_host_fusion_mesh_al(sfmx_ctx* ctx, const uint8_t* const* images, int on
       if (nf == 0)
         rc = sfmx_sdist_set_target(ctx, g.sd, nullptr, 0, nullptr, 0, 0, &dp);
       else
-        rc = clean ? sfmx_sdist_set_target_clean(ctx, g.sd, g.cl, &dp) : sfmx_sdist_set_target_fusion(ctx, g.sd, g.fu, &dp);
+        rc = simplified ? sfmx_sdist_set_target(ctx, g.sd, mv, nv, mf, nf, 1, &dp)
+             : clean    ? sfmx_sdist_set_target_clean(ctx, g.sd, g.cl, &dp)
+                        : sfmx_sdist_set_target_fusion(ctx, g.sd, g.fu, &dp);
     }
     if (rc == SFMX_OK) rc = sfmx_sdist_query(ctx, g.sd, gq.data(), (int)d2.size(), 0, d2.data(), nullptr);
     if (rc != SFMX_OK) {

@@ -147,4 +147,19 @@ int sfmx_host_fusion_mesh_al(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
                              sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
                              sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_al with the final surface simplified by exact vertex clustering.  simplify = NULL: exactly
+// sfmx_host_fusion_mesh_al (simplify_counts is not touched).  Otherwise the order is: extract (with normals when app is given) ->
+// clean (when given) -> simplify on the device (sfmx_simplify_clean, or sfmx_simplify_fusion without clean) -> with app the
+// SIMPLIFIED device vertices are shaded with their own normals -> with gt the simplified mesh is evaluated from where it lies on
+// the device -> the result arrays and the PLY are the simplified mesh.  simplify_counts (optional) int32 [5]: clusters,
+// degenerate faces, duplicate faces, and the vertices and faces that went into the stage (zeros when the surface had no faces
+// before it).  A surface that falls into one cell has no faces left (the PLY is then skipped with its WARN line).
+int sfmx_host_fusion_mesh_sp(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, sfmx_fusion_result_ex* res,
+                             const char* ply_path, char* warn, int warn_cap);
 }

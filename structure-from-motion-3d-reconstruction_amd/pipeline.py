@@ -183,6 +183,7 @@ class FusionResultEx(ctypes.Structure):
 APPEARANCE_KEYS = ("depth_tol", "cull", "fill")
 CONSISTENCY_KEYS = ("rel_tol", "reproj_px", "min_support")
 CLEAN_KEYS = ("min_faces", "min_permille")
+SIMPLIFY_KEYS = ("factor", "cell", "origin")
 EVALUATE_KEYS = ("gt_verts", "gt_faces", "d_max", "tau", "percentile", "cell")
 EVALUATION_FIELDS = ("accuracy", "acc_within", "acc_mean", "acc_max", "n_rec", "completeness", "comp_within", "n_gt")
 
@@ -270,7 +271,7 @@ def _split_fusion_params(params: dict):
 
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
-         consistency=False, clean=False, evaluate=None, render=None, align=False, **params) -> dict:
+         consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -299,7 +300,12 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     every later pair's view is first registered to the volume integrated so far and enters it, and the shade views
     of appearance, at its refined view.  The dict gains alignment = [dict(pair, status, iterations, n, rms, view), ...], one per
     aligned pair: status as capi.ALIGN_STATUS, n and rms = sqrt(e / n) of the last evaluation, view the refined camera.  A pair
-    whose alignment ends TOO_FEW or DEGENERATE keeps its given view (one WARN line).  Not together with consistency."""
+    whose alignment ends TOO_FEW or DEGENERATE keeps its given view (one WARN line).  Not together with consistency.
+    simplify: True, or dict(factor=2.0, cell=, origin=) -- the surface (the cleaned one with clean) is simplified on the device by
+    exact vertex clustering on a grid of `factor` voxels, or of `cell` in the volume's units (not both), whose
+    corner `origin` defaults to the volume's; with appearance the simplified vertices are shaded with their own normals, and
+    evaluate measures the simplified mesh.  The dict gains simplify = dict(clusters=, degenerate=, duplicates=, verts_before=,
+    faces_before=)."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -341,6 +347,17 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             raise TypeError(f"unknown clean parameters {sorted(unknown)}")
         lp = capi.clean_params(**lkw)
         lcounts = np.zeros(4, np.int32)
+    mp = None
+    if simplify:
+        mkw = {} if simplify is True else dict(simplify)
+        unknown = set(mkw) - set(SIMPLIFY_KEYS)
+        if unknown:
+            raise TypeError(f"unknown simplify parameters {sorted(unknown)}")
+        if "factor" in mkw and "cell" in mkw:
+            raise TypeError("simplify takes factor (voxels) or cell (a length), not both")
+        mcell = float(mkw["cell"]) if "cell" in mkw else float(mkw.get("factor", 2.0)) * float(voxel)
+        mp = capi.simplify_params(mcell, origin=mkw.get("origin", origin))
+        mcounts = np.zeros(5, np.int32)
     gt = None
     if evaluate is not None:
         ekw = dict(evaluate)
@@ -389,12 +406,20 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         seed = int(gkw.pop("seed", 1))
         aouts = (capi.AlignResult * max(len(pr), 1))()
         aq = AlignRequest(seed, capi.align_params(disp_min=fp.disp_min, **gkw), aouts)
-    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None:
+    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if aq is not None:
+        if mp is not None:
+            rc = lib.sfmx_host_fusion_mesh_sp(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None,
+                                              byref(rq) if rq is not None else None, byref(aq) if aq is not None else None,
+                                              byref(mp), mcounts.ctypes.data_as(POINTER(c_int)), *tail)
+        elif aq is not None:
             rc = lib.sfmx_host_fusion_mesh_al(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -438,6 +463,8 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             out["consistency"] = dict(valid=[int(v) for v in done[:, 0]], kept=[int(v) for v in done[:, 1]])
         if lp is not None:
             out["clean"] = dict(zip(("components", "largest", "verts_removed", "faces_removed"), (int(v) for v in lcounts)))
+        if mp is not None:
+            out["simplify"] = dict(zip(("clusters", "degenerate", "duplicates", "verts_before", "faces_before"), (int(v) for v in mcounts)))
         if gt is not None:
             out["evaluation"] = ev.asdict()
         if rq is not None:
@@ -510,7 +537,8 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     'consistency' (True or a dict, as fuse) filters the pairs' disparity maps against each other first; 'clean' (True or a
     dict, as fuse) removes the surface's small connected components; 'evaluate' (a dict, as fuse) evaluates the final mesh against
     a ground-truth mesh; 'render' (a dict, as fuse) ray casts the volume from further cameras; 'align' (True or a dict, as fuse) registers each later
-    pair's view to the volume before it enters it.  The run itself, its log and every other output are unchanged.
+    pair's view to the volume before it enters it; 'simplify' (True or a dict, as fuse) simplifies the final surface by exact vertex
+    clustering.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -577,8 +605,10 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         evaluate = fz.pop("evaluate", None)
         render = fz.pop("render", None)
         align = fz.pop("align", False)
+        simplify = fz.pop("simplify", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
-                                 appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align, **fz)
+                                 appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align,
+                                 simplify=simplify, **fz)
     return out
 
 

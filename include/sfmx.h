@@ -675,6 +675,66 @@ int sfmx_simplify_device_mesh(const sfmx_simplify* sp, const double** verts, con
 /* device time (us) from the first to the last launch of the last run when timing is on (sfmx_set_timing), else 0 */
 double sfmx_simplify_last_us(const sfmx_simplify* sp);
 
+/* ---- smoothing a triangle mesh: exact Taubin lambda|mu filtering ------------------------------------------- */
+/* Fixed point: per vertex and component q = (x - origin) / unit and Q = (int64)floor(q 2^20 + 0.5), in this order in IEEE double
+ * without contraction.
+ * Edges: face (a, b, c) has the directed edges a->b, b->c, c->a; one with equal ends is ignored (the face's other edges still
+ * count).  An edge is an unordered pair {lo < hi} that some directed edge uses; fwd counts its uses as lo->hi and bwd as hi->lo.
+ * It is regular when fwd == 1 && bwd == 1, boundary when fwd + bwd == 1, irregular otherwise.
+ * Vertices: cnt is the number of edges at a vertex (its distinct neighbours N).  A vertex is isolated when cnt == 0; with pin = 1
+ * it is pinned when at least one of its edges is not regular (with pin = 0 none is); it moves when it is neither.
+ * Steps: 2 iters Jacobi steps, numbered from 0, each reading the positions the previous one left; the factor f is lambda on even
+ * and mu on odd steps.  For a moving vertex and each component S = sum over N of Q_j (int64), m = (double)S / (double)cnt,
+ * d = m - (double)Q, Q' = Q + (int64)floor(f d + 0.5), with no fma anywhere; other vertices keep their Q.  |Q'| > 2^38 at any
+ * step fails the call (diverged).
+ * Output: a moving vertex gets origin + ((double)Q 2^-20) unit, a pinned or isolated one keeps its input bytes; flags uint8 [n]
+ * has bit 0 pinned and bit 1 isolated.  Faces are not touched and normals are not an input.  The sums are integers, so every
+ * output is bit-identical to the NumPy restatement in tests/smooth_ref.py whatever the schedule. */
+typedef struct sfmx_smooth sfmx_smooth;  /* device work buffers and the last result; they grow on demand and are kept */
+typedef struct sfmx_smooth_params {
+  double unit;       /* the length of one fixed-point unit 2^20; finite, > 0; no default (the voxel in the pipeline) */
+  double origin[3];  /* finite (default 0) */
+  double lambda;     /* 0 < lambda <= 1 (default 0.5) */
+  double mu;         /* -1 <= mu <= 0 (default -0.53); 0 is plain Laplacian smoothing */
+  int iters;         /* lambda|mu pairs, 1 .. 64 (default 10) */
+  int pin;           /* 0 or 1 (default 1) */
+} sfmx_smooth_params;
+void sfmx_smooth_default_params(sfmx_smooth_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_smooth_check_params(const sfmx_smooth_params* p);
+int sfmx_smooth_create(sfmx_ctx* ctx, sfmx_smooth** out);
+void sfmx_smooth_destroy(sfmx_ctx* ctx, sfmx_smooth* sm);
+/* verts double [n][3], faces int32 [m][3]; host pointers or (on_device = 1) device pointers, 0 <= n < 2^24, 0 <= m < 2^30.
+ * SFMX_ERR_INVALID (found on the device, nothing is accessed through a bad index; the object stays usable and no result is
+ * left) for a coordinate that is not finite or with |q| > 2^18, a face index outside [0, n), and divergence.  A mesh with more
+ * than 2^30 - 1024 edges is refused the same way: the neighbour lists are indexed by int32. */
+int sfmx_smooth_run(sfmx_ctx* ctx, sfmx_smooth* sm, const double* verts, int n, const int32_t* faces, int m, int on_device,
+                    const sfmx_smooth_params* p);
+/* the same for the surface the last sfmx_fusion_extract / _extract_normals with arrays left on the device inside fu, and for the
+ * cleaned surface of the last successful run on cl; no host round trip.  SFMX_ERR_INVALID when there is none. */
+int sfmx_smooth_fusion(sfmx_ctx* ctx, sfmx_smooth* sm, const sfmx_fusion* fu, const sfmx_smooth_params* p);
+int sfmx_smooth_clean(sfmx_ctx* ctx, sfmx_smooth* sm, const sfmx_clean* cl, const sfmx_smooth_params* p);
+/* the last successful run to the host: verts_out double [n][3], flags_out uint8 [n]; either may be NULL.  SFMX_ERR_INVALID
+ * before a successful run; a call that fails for any reason (parameters included) leaves no result. */
+int sfmx_smooth_read(sfmx_ctx* ctx, sfmx_smooth* sm, double* verts_out, uint8_t* flags_out);
+/* vertices and faces (n, m) of the last successful run; either pointer may be NULL.  SFMX_ERR_INVALID (and zeros) before a
+ * successful run; needs no context. */
+int sfmx_smooth_sizes(const sfmx_smooth* sm, int* n, int* m);
+/* of the last successful run: edges, boundary and irregular edges, pinned and isolated vertices; any pointer may be NULL.
+ * SFMX_ERR_INVALID (and zeros) before a successful run; needs no context. */
+int sfmx_smooth_counts(const sfmx_smooth* sm, int* edges, int* boundary_edges, int* irregular_edges, int* pinned, int* isolated);
+/* the smoothed vertices and the input's faces on the device and *n_faces = m (for sfmx_simplify_run, sfmx_shade_vertices and
+ * sfmx_sdist_set_target / _query with on_device = 1; the normals to go with them are the caller's own, unchanged); any pointer
+ * may be NULL.  The faces are the object's own copy when the run had host pointers, else the pointer the run was given: they
+ * live as long as their owner keeps them.  Returns n, or -1 before a successful run.  Valid until the next run on sm. */
+int sfmx_smooth_device_mesh(const sfmx_smooth* sm, const double** verts, const int32_t** faces, int* n_faces);
+/* the smoothed vertices, and the normals the run's source carried on the device: those of the extraction (sfmx_smooth_fusion) or
+ * of the cleaned surface (sfmx_smooth_clean), unchanged and still owned by that object; *normals is NULL when it had none and
+ * after sfmx_smooth_run.  Returns n, or -1 before a successful run.  Valid until the next run on sm. */
+int sfmx_smooth_device_surface(const sfmx_smooth* sm, const double** verts, const double** normals);
+/* device time (us) from the first to the last launch of the last run when timing is on (sfmx_set_timing), else 0 */
+double sfmx_smooth_last_us(const sfmx_smooth* sm);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

@@ -55,6 +55,9 @@ SYMBOLS = [
     "sfmx_simplify_default_params", "sfmx_simplify_check_params", "sfmx_simplify_create", "sfmx_simplify_destroy", "sfmx_simplify_run",
     "sfmx_simplify_fusion", "sfmx_simplify_clean", "sfmx_simplify_read", "sfmx_simplify_sizes", "sfmx_simplify_counts",
     "sfmx_simplify_device_surface", "sfmx_simplify_device_mesh", "sfmx_simplify_last_us",
+    "sfmx_smooth_default_params", "sfmx_smooth_check_params", "sfmx_smooth_create", "sfmx_smooth_destroy", "sfmx_smooth_run",
+    "sfmx_smooth_fusion", "sfmx_smooth_clean", "sfmx_smooth_read", "sfmx_smooth_sizes", "sfmx_smooth_counts",
+    "sfmx_smooth_device_mesh", "sfmx_smooth_device_surface", "sfmx_smooth_last_us",
 ]
 
 
@@ -246,6 +249,42 @@ def simplify_check_params(cell=0.0, **kw) -> bool:
     return load_library().sfmx_simplify_check_params(byref(simplify_params(cell, **kw))) == SFMX_OK
 
 
+class SmoothParams(ctypes.Structure):
+    _fields_ = [("unit", c_double), ("origin", c_double * 3), ("lam", c_double), ("mu", c_double), ("iters", c_int), ("pin", c_int)]
+
+
+# unit has no default (a length in the caller's units: the voxel in the pipeline)
+SMOOTH_DEFAULTS = dict(origin=(0.0, 0.0, 0.0), lam=0.5, mu=-0.53, iters=10, pin=1)
+SMOOTH_COUNTS = ("edges", "boundary_edges", "irregular_edges", "pinned", "isolated")
+
+
+def smooth_params(unit=0.0, **kw) -> SmoothParams:
+    unknown = set(kw) - set(SMOOTH_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown smooth parameters {sorted(unknown)}")
+    kw = {**SMOOTH_DEFAULTS, **kw}
+    p = SmoothParams()
+    p.unit = float(unit)
+    p.origin[:] = [float(v) for v in kw["origin"]]
+    p.lam, p.mu = float(kw["lam"]), float(kw["mu"])
+    if int(kw["iters"]) != kw["iters"] or int(kw["pin"]) != kw["pin"]:
+        raise TypeError("smooth parameters iters and pin are integers")
+    p.iters, p.pin = int(kw["iters"]), int(kw["pin"])
+    return p
+
+
+def smooth_default_params() -> dict:
+    """sfmx_smooth_default_params as a dict (needs no device)"""
+    p = SmoothParams()
+    load_library().sfmx_smooth_default_params(byref(p))
+    return dict(unit=p.unit, origin=tuple(p.origin), lam=p.lam, mu=p.mu, iters=p.iters, pin=p.pin)
+
+
+def smooth_check_params(unit=0.0, **kw) -> bool:
+    """True if sfmx_smooth_run / _fusion / _clean would accept the parameters; needs no device"""
+    return load_library().sfmx_smooth_check_params(byref(smooth_params(unit, **kw))) == SFMX_OK
+
+
 class SdistParams(ctypes.Structure):
     _fields_ = [("d_max", c_double), ("cell", c_double)]
 
@@ -381,6 +420,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_raycast_last_samples.restype = c_uint64
         _lib.sfmx_align_last_us.restype = c_double
         _lib.sfmx_simplify_last_us.restype = c_double
+        _lib.sfmx_smooth_last_us.restype = c_double
     return _lib
 
 
@@ -841,6 +881,94 @@ class Simplify:
     def close(self):
         if self.h_:
             self.ctx.lib.sfmx_simplify_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Smooth:
+    """sfmx_smooth: exact Taubin lambda|mu smoothing of a triangle mesh; the work buffers are kept between calls."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_smooth_create(ctx.h_, byref(self.h_)))
+
+    def run(self, verts, faces, n=None, m=None, unit=0.0, **params):
+        """verts float64 [n][3] and faces int32 [m][3]: numpy arrays, or ints (device pointers) with n and m given.  unit is
+        required; params: SMOOTH_DEFAULTS keys.  Returns counts()."""
+        p = smooth_params(unit, **params)
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int):
+            raise TypeError("verts and faces: both host arrays or both device pointers")
+        if on_dev:
+            pv, pf = c_void_p(verts), c_void_p(faces)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            n, m = len(verts), len(faces)
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+        self.ctx._chk(self.ctx.lib.sfmx_smooth_run(self.ctx.h_, self.h_, pv, c_int(n), pf, c_int(m), c_int(1 if on_dev else 0), byref(p)))
+        return self.counts()
+
+    def fusion(self, fu: "Fusion", unit=0.0, **params):
+        """the surface fu.extract() / fu.extract_normals() left on the device; returns counts()"""
+        p = smooth_params(unit, **params)
+        self.ctx._chk(self.ctx.lib.sfmx_smooth_fusion(self.ctx.h_, self.h_, fu.h_, byref(p)))
+        return self.counts()
+
+    def clean(self, cl: "Clean", unit=0.0, **params):
+        """the cleaned surface of cl's last run, on the device; returns counts()"""
+        p = smooth_params(unit, **params)
+        self.ctx._chk(self.ctx.lib.sfmx_smooth_clean(self.ctx.h_, self.h_, cl.h_, byref(p)))
+        return self.counts()
+
+    def sizes(self):
+        """(n, m) of the last successful run; raises before one"""
+        s = [c_int(0) for _ in range(2)]
+        rc = self.ctx.lib.sfmx_smooth_sizes(self.h_, *[byref(x) for x in s])
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_smooth_sizes: no successful run")
+        return tuple(x.value for x in s)
+
+    def counts(self) -> dict:
+        """dict(edges, boundary_edges, irregular_edges, pinned, isolated) of the last successful run; raises before one"""
+        s = [c_int(0) for _ in range(5)]
+        rc = self.ctx.lib.sfmx_smooth_counts(self.h_, *[byref(x) for x in s])
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_smooth_counts: no successful run")
+        return dict(zip(SMOOTH_COUNTS, (x.value for x in s)))
+
+    def read(self):
+        """the last run: dict(verts f64 [n][3], flags u8 [n]: bit 0 pinned, bit 1 isolated), sized by what the library says it
+        will copy"""
+        n, _ = self.sizes()
+        verts, flags = np.zeros((max(n, 1), 3)), np.zeros(max(n, 1), np.uint8)
+        self.ctx._chk(self.ctx.lib.sfmx_smooth_read(self.ctx.h_, self.h_, _p(verts, c_double), _p(flags, ctypes.c_uint8)))
+        return dict(verts=verts[:n].copy(), flags=flags[:n].copy())
+
+    def device_mesh(self):
+        """(n, device pointer of the smoothed vertices, of the input's faces, m); n = -1 before a successful run"""
+        v, f, m = c_void_p(), c_void_p(), c_int(0)
+        n = int(self.ctx.lib.sfmx_smooth_device_mesh(self.h_, byref(v), byref(f), byref(m)))
+        return n, v.value, f.value, int(m.value)
+
+    def device_surface(self):
+        """(n, device pointer of the smoothed vertices, of the source's normals or None); n = -1 before a successful run"""
+        v, nr = c_void_p(), c_void_p()
+        n = int(self.ctx.lib.sfmx_smooth_device_surface(self.h_, byref(v), byref(nr)))
+        return n, v.value, nr.value
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_smooth_last_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_smooth_destroy(self.ctx.h_, self.h_)
             self.h_ = c_void_p()
 
     def __del__(self):
@@ -1456,6 +1584,9 @@ class Context:
 
     def simplify(self) -> "Simplify":
         return Simplify(self)
+
+    def smooth(self) -> "Smooth":
+        return Smooth(self)
 
     def sdist(self) -> "Sdist":
         return Sdist(self)

@@ -162,4 +162,20 @@ int sfmx_host_fusion_mesh_sp(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
                              const sfmx_simplify_params* simplify, int32_t* simplify_counts, sfmx_fusion_result_ex* res,
                              const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_sp with the surface smoothed by the exact Taubin lambda|mu filter between cleaning and
+// simplifying.  smooth = NULL: exactly sfmx_host_fusion_mesh_sp (smooth_counts is not touched).  Otherwise the order is: extract
+// (with normals when app is given) -> clean (when given) -> smooth on the device (sfmx_smooth_clean, or sfmx_smooth_fusion
+// without clean) -> simplify (when given; sfmx_simplify_run on the smooth object's device mesh with the normals of the stage
+// before) -> with app the final device vertices are shaded (a smoothed vertex with the normal it had) -> with gt the final mesh
+// is evaluated from where it lies on the device -> the result arrays and the PLY are the final mesh.  smooth->unit and origin are
+// used as given (pipeline.fuse passes the voxel and the volume's origin).  smooth_counts (optional) int32 [5]: edges, boundary
+// edges, irregular edges, pinned and isolated vertices (zeros when the surface had no faces before the stage).
+int sfmx_host_fusion_mesh_sm(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
 }

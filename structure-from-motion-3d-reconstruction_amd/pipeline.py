@@ -184,6 +184,7 @@ APPEARANCE_KEYS = ("depth_tol", "cull", "fill")
 CONSISTENCY_KEYS = ("rel_tol", "reproj_px", "min_support")
 CLEAN_KEYS = ("min_faces", "min_permille")
 SIMPLIFY_KEYS = ("factor", "cell", "origin")
+SMOOTH_KEYS = ("iters", "lam", "mu", "pin", "unit", "origin")
 EVALUATE_KEYS = ("gt_verts", "gt_faces", "d_max", "tau", "percentile", "cell")
 EVALUATION_FIELDS = ("accuracy", "acc_within", "acc_mean", "acc_max", "n_rec", "completeness", "comp_within", "n_gt")
 
@@ -271,7 +272,7 @@ def _split_fusion_params(params: dict):
 
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
-         consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, **params) -> dict:
+         consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -305,7 +306,13 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     exact vertex clustering on a grid of `factor` voxels, or of `cell` in the volume's units (not both), whose
     corner `origin` defaults to the volume's; with appearance the simplified vertices are shaded with their own normals, and
     evaluate measures the simplified mesh.  The dict gains simplify = dict(clusters=, degenerate=, duplicates=, verts_before=,
-    faces_before=)."""
+    faces_before=).
+    smooth: True, or dict(iters=10, lam=0.5, mu=-0.53, pin=1, unit=, origin=) -- the surface (the cleaned one with clean) is smoothed
+    on the device by the exact Taubin lambda|mu filter before it is simplified, shaded, evaluated and written: `iters`
+    pairs of a lambda and a mu step over each vertex's distinct neighbours, with the vertices of every edge that is not used once in
+    each direction held in place (pin=1).  unit (the length 2^20 fixed-point steps stand for) defaults to the voxel and origin to
+    the volume's.  Normals stay with their vertices.  The dict gains smooth = dict(edges=, boundary_edges=, irregular_edges=,
+    pinned=, isolated=)."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -358,6 +365,14 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         mcell = float(mkw["cell"]) if "cell" in mkw else float(mkw.get("factor", 2.0)) * float(voxel)
         mp = capi.simplify_params(mcell, origin=mkw.get("origin", origin))
         mcounts = np.zeros(5, np.int32)
+    tp = None
+    if smooth:
+        tkw = {} if smooth is True else dict(smooth)
+        unknown = set(tkw) - set(SMOOTH_KEYS)
+        if unknown:
+            raise TypeError(f"unknown smooth parameters {sorted(unknown)}")
+        tp = capi.smooth_params(float(tkw.pop("unit", voxel)), origin=tkw.pop("origin", origin), **tkw)
+        tcounts = np.zeros(5, np.int32)
     gt = None
     if evaluate is not None:
         ekw = dict(evaluate)
@@ -406,12 +421,22 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         seed = int(gkw.pop("seed", 1))
         aouts = (capi.AlignResult * max(len(pr), 1))()
         aq = AlignRequest(seed, capi.align_params(disp_min=fp.disp_min, **gkw), aouts)
-    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None:
+    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if mp is not None:
+        if tp is not None:
+            rc = lib.sfmx_host_fusion_mesh_sm(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None,
+                                              byref(rq) if rq is not None else None, byref(aq) if aq is not None else None,
+                                              byref(mp) if mp is not None else None,
+                                              mcounts.ctypes.data_as(POINTER(c_int)) if mp is not None else None,
+                                              byref(tp), tcounts.ctypes.data_as(POINTER(c_int)), *tail)
+        elif mp is not None:
             rc = lib.sfmx_host_fusion_mesh_sp(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -465,6 +490,8 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             out["clean"] = dict(zip(("components", "largest", "verts_removed", "faces_removed"), (int(v) for v in lcounts)))
         if mp is not None:
             out["simplify"] = dict(zip(("clusters", "degenerate", "duplicates", "verts_before", "faces_before"), (int(v) for v in mcounts)))
+        if tp is not None:
+            out["smooth"] = dict(zip(capi.SMOOTH_COUNTS, (int(v) for v in tcounts)))
         if gt is not None:
             out["evaluation"] = ev.asdict()
         if rq is not None:
@@ -538,7 +565,7 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     dict, as fuse) removes the surface's small connected components; 'evaluate' (a dict, as fuse) evaluates the final mesh against
     a ground-truth mesh; 'render' (a dict, as fuse) ray casts the volume from further cameras; 'align' (True or a dict, as fuse) registers each later
     pair's view to the volume before it enters it; 'simplify' (True or a dict, as fuse) simplifies the final surface by exact vertex
-    clustering.  The run itself, its log and every other output are unchanged.
+    clustering; 'smooth' (True or a dict, as fuse) smooths it with the exact Taubin filter first.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -606,9 +633,10 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         render = fz.pop("render", None)
         align = fz.pop("align", False)
         simplify = fz.pop("simplify", False)
+        smooth = fz.pop("smooth", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
                                  appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align,
-                                 simplify=simplify, **fz)
+                                 simplify=simplify, smooth=smooth, **fz)
     return out
 
 

@@ -735,6 +735,68 @@ int sfmx_smooth_device_surface(const sfmx_smooth* sm, const double** verts, cons
 /* device time (us) from the first to the last launch of the last run when timing is on (sfmx_set_timing), else 0 */
 double sfmx_smooth_last_us(const sfmx_smooth* sm);
 
+/* ---- filling the small holes of a triangle mesh: exact centroid fans ---------------------------------------- */
+/* Fixed point, directed edges, the edge table {lo < hi} with fwd / bwd, and regular / boundary / irregular: as for sfmx_smooth
+ * above.
+ * Gaps: a boundary edge used as a->b has the gap half-edge b->a (tail b, head a).  out(v) and in(v) count the gap half-edges
+ * that leave and enter v.  A vertex is simple when out == 1 && in == 1 and none of its edges is irregular, and complex when it
+ * has a gap half-edge and is not simple.  next(v) of a simple v is the head of its one outgoing gap half-edge.
+ * Loops: a cycle v0 -> next(v0) -> ... -> v0 of L >= 3 distinct vertices that are all simple; its leader is its smallest vertex
+ * index and it is traversed from the leader along next.  It is filled when L <= max_edges.  Chains through a complex vertex and
+ * longer cycles are left alone (the gaps at a complex vertex are not paired up).
+ * Filling, in ascending leader order: L == 3 gives the face (v0, v1, v2) and no vertex.  L > 3 gives one new vertex c (numbered
+ * n, n + 1, ... in loop order) and the faces (v_i, v_(i+1) mod L, c), i = 0 .. L-1: per component S = sum of Q over the loop
+ * (int64), Qc = floor((2 S + L) / (2 L)) (a true floor), position origin + ((double)Qc 2^-20) unit.  With normals the new
+ * vertex gets s / ln, or 0.0 unless ln > 0, where s starts at +0.0 and adds the loop's normals one by one in traversal order and
+ * ln = sqrt((s0 s0 + s1 s1) + s2 s2), in IEEE double with no fma (a sum that becomes infinite is outside the contract).
+ * Output: verts_out [n + K][3], normals_out [n + K][3], faces_out [m + F][3]; the first n (m) rows are the input bytes, the new
+ * faces follow loop by loop.  Every filled rim edge becomes regular, a second run with the same parameters fills nothing, and
+ * every output is bit-identical to the NumPy restatement in tests/fill_ref.py whatever the schedule. */
+typedef struct sfmx_fill sfmx_fill;  /* device work buffers and the last result; they grow on demand and are kept */
+typedef struct sfmx_fill_params {
+  double unit;       /* the length of one fixed-point unit 2^20; finite, > 0; no default (the voxel in the pipeline) */
+  double origin[3];  /* finite (default 0) */
+  int max_edges;     /* the longest loop that is filled, 3 .. 1024 (default 32) */
+} sfmx_fill_params;
+void sfmx_fill_default_params(sfmx_fill_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_fill_check_params(const sfmx_fill_params* p);
+int sfmx_fill_create(sfmx_ctx* ctx, sfmx_fill** out);
+void sfmx_fill_destroy(sfmx_ctx* ctx, sfmx_fill* fl);
+/* verts and normals double [n][3] (normals may be NULL), faces int32 [m][3]; host pointers or (on_device = 1) device pointers
+ * that are not fl's own result arrays, 0 <= n < 2^24, 0 <= m < 2^30.  SFMX_ERR_INVALID (found on the device, nothing is accessed
+ * through a bad index; the object stays usable and no result is left) for a coordinate that is not finite or with |q| > 2^18, a
+ * face index outside [0, n), and n + K >= 2^24 or m + F >= 2^30.  A mesh with more than 2^30 - 1024 edges is refused the same
+ * way: the offsets of the new faces are int32. */
+int sfmx_fill_run(sfmx_ctx* ctx, sfmx_fill* fl, const double* verts, const double* normals, int n, const int32_t* faces, int m,
+                  int on_device, const sfmx_fill_params* p);
+/* the same for the surface the last sfmx_fusion_extract / _extract_normals with arrays left on the device inside fu (with its
+ * normals if it made them), and for the cleaned surface of the last successful run on cl; no host round trip.
+ * SFMX_ERR_INVALID when there is none. */
+int sfmx_fill_fusion(sfmx_ctx* ctx, sfmx_fill* fl, const sfmx_fusion* fu, const sfmx_fill_params* p);
+int sfmx_fill_clean(sfmx_ctx* ctx, sfmx_fill* fl, const sfmx_clean* cl, const sfmx_fill_params* p);
+/* the last successful run to the host: verts_out and normals_out double [n + K][3], faces_out int32 [m + F][3]; any may be
+ * NULL.  SFMX_ERR_INVALID before a successful run, and for normals_out after a run without normals; a call that fails for any
+ * reason (parameters included) leaves no result. */
+int sfmx_fill_read(sfmx_ctx* ctx, sfmx_fill* fl, double* verts_out, double* normals_out, int32_t* faces_out);
+/* input and output vertices and faces (n, m, n + K, m + F) of the last successful run; any pointer may be NULL.
+ * SFMX_ERR_INVALID (and zeros) before a successful run; needs no context. */
+int sfmx_fill_sizes(const sfmx_fill* fl, int* n, int* m, int* n_out, int* m_out);
+/* of the last successful run: edges, boundary and irregular edges and complex vertices of the input, the loops filled, their
+ * edges, K and F; any pointer may be NULL.  SFMX_ERR_INVALID (and zeros) before a successful run; needs no context. */
+int sfmx_fill_counts(const sfmx_fill* fl, int* edges, int* boundary_edges, int* irregular_edges, int* complex_vertices, int* filled_loops,
+                     int* filled_edges, int* new_verts, int* new_faces);
+/* the filled mesh on the device, the object's own arrays: *n_verts = n + K and *n_faces = m + F (for sfmx_smooth_run,
+ * sfmx_simplify_run, sfmx_shade_vertices and sfmx_sdist_set_target / _query with on_device = 1); any pointer may be NULL.
+ * Returns n + K, or -1 before a successful run.  Valid until the next run on fl. */
+int sfmx_fill_device_mesh(const sfmx_fill* fl, const double** verts, const int32_t** faces, int* n_verts, int* n_faces);
+/* the filled vertices and their normals, the object's own arrays of n + K rows: after a fill the vertex count differs from the
+ * source's, so every later stage takes its normals from here.  *normals is NULL after a run without normals.  Returns n + K, or
+ * -1 before a successful run.  Valid until the next run on fl. */
+int sfmx_fill_device_surface(const sfmx_fill* fl, const double** verts, const double** normals);
+/* device time (us) from the first to the last launch of the last run when timing is on (sfmx_set_timing), else 0 */
+double sfmx_fill_last_us(const sfmx_fill* fl);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

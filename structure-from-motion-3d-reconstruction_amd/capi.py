@@ -58,6 +58,9 @@ SYMBOLS = [
     "sfmx_smooth_default_params", "sfmx_smooth_check_params", "sfmx_smooth_create", "sfmx_smooth_destroy", "sfmx_smooth_run",
     "sfmx_smooth_fusion", "sfmx_smooth_clean", "sfmx_smooth_read", "sfmx_smooth_sizes", "sfmx_smooth_counts",
     "sfmx_smooth_device_mesh", "sfmx_smooth_device_surface", "sfmx_smooth_last_us",
+    "sfmx_fill_default_params", "sfmx_fill_check_params", "sfmx_fill_create", "sfmx_fill_destroy", "sfmx_fill_run",
+    "sfmx_fill_fusion", "sfmx_fill_clean", "sfmx_fill_read", "sfmx_fill_sizes", "sfmx_fill_counts",
+    "sfmx_fill_device_mesh", "sfmx_fill_device_surface", "sfmx_fill_last_us",
 ]
 
 
@@ -285,6 +288,41 @@ def smooth_check_params(unit=0.0, **kw) -> bool:
     return load_library().sfmx_smooth_check_params(byref(smooth_params(unit, **kw))) == SFMX_OK
 
 
+class FillParams(ctypes.Structure):
+    _fields_ = [("unit", c_double), ("origin", c_double * 3), ("max_edges", c_int)]
+
+
+# unit has no default (a length in the caller's units: the voxel in the pipeline)
+FILL_DEFAULTS = dict(origin=(0.0, 0.0, 0.0), max_edges=32)
+FILL_COUNTS = ("edges", "boundary_edges", "irregular_edges", "complex_vertices", "filled_loops", "filled_edges", "new_verts", "new_faces")
+
+
+def fill_params(unit=0.0, **kw) -> FillParams:
+    unknown = set(kw) - set(FILL_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown fill parameters {sorted(unknown)}")
+    kw = {**FILL_DEFAULTS, **kw}
+    p = FillParams()
+    p.unit = float(unit)
+    p.origin[:] = [float(v) for v in kw["origin"]]
+    if int(kw["max_edges"]) != kw["max_edges"]:
+        raise TypeError("fill parameter max_edges is an integer")
+    p.max_edges = int(kw["max_edges"])
+    return p
+
+
+def fill_default_params() -> dict:
+    """sfmx_fill_default_params as a dict (needs no device)"""
+    p = FillParams()
+    load_library().sfmx_fill_default_params(byref(p))
+    return dict(unit=p.unit, origin=tuple(p.origin), max_edges=p.max_edges)
+
+
+def fill_check_params(unit=0.0, **kw) -> bool:
+    """True if sfmx_fill_run / _fusion / _clean would accept the parameters; needs no device"""
+    return load_library().sfmx_fill_check_params(byref(fill_params(unit, **kw))) == SFMX_OK
+
+
 class SdistParams(ctypes.Structure):
     _fields_ = [("d_max", c_double), ("cell", c_double)]
 
@@ -421,6 +459,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_align_last_us.restype = c_double
         _lib.sfmx_simplify_last_us.restype = c_double
         _lib.sfmx_smooth_last_us.restype = c_double
+        _lib.sfmx_fill_last_us.restype = c_double
     return _lib
 
 
@@ -977,6 +1016,102 @@ class Smooth:
         except Exception:
             pass
 
+
+
+class Fill:
+    """sfmx_fill: exact filling of a triangle mesh's small holes by centroid fans; the work buffers are kept between
+    calls."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_fill_create(ctx.h_, byref(self.h_)))
+
+    def run(self, verts, faces, normals=None, n=None, m=None, unit=0.0, **params):
+        """verts / normals float64 [n][3] and faces int32 [m][3]: numpy arrays, or ints (device pointers, not this object's own
+        result) with n and m given; normals may be None.  unit is required; params: FILL_DEFAULTS keys.  Returns counts()."""
+        p = fill_params(unit, **params)
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int) or (normals is not None and on_dev != isinstance(normals, int)):
+            raise TypeError("verts, normals and faces: all host arrays or all device pointers")
+        if on_dev:
+            pv, pf, pn = c_void_p(verts), c_void_p(faces), (c_void_p(normals) if normals is not None else None)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            n, m = len(verts), len(faces)
+            normals = None if normals is None else _f64(normals).reshape(-1, 3)
+            assert normals is None or len(normals) == n
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+            pn = normals.ctypes.data_as(c_void_p) if normals is not None else None
+        self.ctx._chk(self.ctx.lib.sfmx_fill_run(self.ctx.h_, self.h_, pv, pn, c_int(n), pf, c_int(m), c_int(1 if on_dev else 0), byref(p)))
+        return self.counts()
+
+    def fusion(self, fu: "Fusion", unit=0.0, **params):
+        """the surface fu.extract() / fu.extract_normals() left on the device; returns counts()"""
+        p = fill_params(unit, **params)
+        self.ctx._chk(self.ctx.lib.sfmx_fill_fusion(self.ctx.h_, self.h_, fu.h_, byref(p)))
+        return self.counts()
+
+    def clean(self, cl: "Clean", unit=0.0, **params):
+        """the cleaned surface of cl's last run, on the device; returns counts()"""
+        p = fill_params(unit, **params)
+        self.ctx._chk(self.ctx.lib.sfmx_fill_clean(self.ctx.h_, self.h_, cl.h_, byref(p)))
+        return self.counts()
+
+    def sizes(self):
+        """(n, m, n + K, m + F) of the last successful run; raises before one"""
+        s = [c_int(0) for _ in range(4)]
+        rc = self.ctx.lib.sfmx_fill_sizes(self.h_, *[byref(x) for x in s])
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_fill_sizes: no successful run")
+        return tuple(x.value for x in s)
+
+    def counts(self) -> dict:
+        """dict of FILL_COUNTS of the last successful run; raises before one"""
+        s = [c_int(0) for _ in range(8)]
+        rc = self.ctx.lib.sfmx_fill_counts(self.h_, *[byref(x) for x in s])
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_fill_counts: no successful run")
+        return dict(zip(FILL_COUNTS, (x.value for x in s)))
+
+    def read(self, normals: bool = False):
+        """the last run: dict(verts f64 [n + K][3], faces i32 [m + F][3]), plus normals f64 [n + K][3] when asked for (the run
+        must have had them), sized by what the library says it will copy"""
+        _, _, nv, nf = self.sizes()
+        verts, nrm, faces = np.zeros((max(nv, 1), 3)), np.zeros((max(nv, 1), 3)), np.zeros((max(nf, 1), 3), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_fill_read(self.ctx.h_, self.h_, _p(verts, c_double), _p(nrm, c_double) if normals else None,
+                                                  _p(faces, c_int32)))
+        out = dict(verts=verts[:nv].copy(), faces=faces[:nf].copy())
+        if normals:
+            out["normals"] = nrm[:nv].copy()
+        return out
+
+    def device_mesh(self):
+        """(n + K, device pointer of the filled vertices, of the filled faces, m + F); n + K = -1 before a successful run"""
+        v, f, nv, m = c_void_p(), c_void_p(), c_int(0), c_int(0)
+        n = int(self.ctx.lib.sfmx_fill_device_mesh(self.h_, byref(v), byref(f), byref(nv), byref(m)))
+        return n, v.value, f.value, int(m.value)
+
+    def device_surface(self):
+        """(n + K, device pointer of the filled vertices, of their normals or None); n + K = -1 before a successful run"""
+        v, nr = c_void_p(), c_void_p()
+        n = int(self.ctx.lib.sfmx_fill_device_surface(self.h_, byref(v), byref(nr)))
+        return n, v.value, nr.value
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_fill_last_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_fill_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 class Sdist:
     """sfmx_sdist: squared distance from points to the nearest point of a target triangle mesh.  One target
@@ -1587,6 +1722,9 @@ class Context:
 
     def smooth(self) -> "Smooth":
         return Smooth(self)
+
+    def fill(self) -> "Fill":
+        return Fill(self)
 
     def sdist(self) -> "Sdist":
         return Sdist(self)

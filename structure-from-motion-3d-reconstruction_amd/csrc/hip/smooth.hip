@@ -11,7 +11,7 @@
 //   k_sm_edges    per face: an index outside [0, n) sets the flag and the face is skipped; otherwise each directed edge with two
 //                 different ends goes into an open-addressing table of uint64 keys lo << 32 | hi (all ones = empty, power-of-two
 //                 size >= 4 m): a 64-bit CAS on an empty slot, or a match on the returned occupant, else the next slot of the
-//                 key's probe sequence (sm_slot); then an atomicAdd on the slot's fwd or bwd counter.  Slots are never emptied, no thread waits for another, and a probe
+//                 key's probe sequence (et_slot, sfmx_edge_table.h); then an atomicAdd on the slot's fwd or bwd counter.  Slots are never emptied, no thread waits for another, and a probe
 //                 sequence is bounded by the table size
 //   k_sm_degree   a grid-stride loop over the slots, at most 1 024 blocks: an occupied slot adds 1 to cnt[lo] and cnt[hi]; one that
 //                 is not regular stores the pinned byte of both ends (same value); the three edge counts are summed inside the
@@ -27,6 +27,7 @@
 //                 bytes, the flag byte, and one partial per block of the pinned and the isolated counts
 //   -- the host reads the diverged flag and the partial counts (second synchronisation) --
 // No kernel waits on another workgroup or spins on a memory word.
+#include "sfmx_edge_table.h"
 #include "sfmx_internal.h"
 
 namespace {
@@ -34,7 +35,6 @@ namespace {
 constexpr double SM_SCALE = 1048576.0;            // 2^20: the fixed-point scale
 constexpr double SM_MAX_Q = 262144.0;             // 2^18: the largest |q| of an input coordinate
 constexpr long long SM_MAX_FIXED = 1ll << 38;     // the largest |Q| after a step
-constexpr unsigned long long SM_EMPTY = ~0ull;
 constexpr int SM_PART_BLOCKS = 1024;
 
 // counters (int32 each): two flags, then the partial counts of k_sm_degree [SM_PART_BLOCKS][3] and of k_sm_emit [..][2]
@@ -42,15 +42,6 @@ enum { SM_FLAG = 0, SM_DIVERGED, SM_HEAD = 8 };
 constexpr int SM_EDGE_PART = SM_HEAD;
 constexpr int SM_VERT_PART = SM_EDGE_PART + 3 * SM_PART_BLOCKS;
 constexpr int SM_COUNTERS = SM_VERT_PART + 2 * SM_PART_BLOCKS;
-
-__device__ __forceinline__ unsigned long long sm_hash(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xFF51AFD7ED558CCDull;
-  k ^= k >> 33;
-  k *= 0xC4CEB9FE1A85EC53ull;
-  k ^= k >> 33;
-  return k;
-}
 
 __global__ __launch_bounds__(256) void k_sm_quant(const double* __restrict__ verts, int n, double unit, double o0, double o1, double o2,
                                                   long long* __restrict__ Q, int* __restrict__ counters) {
@@ -67,66 +58,11 @@ __global__ __launch_bounds__(256) void k_sm_quant(const double* __restrict__ ver
   }
 }
 
-// Slot number `probe` of a key's probe sequence.  The first SM_LOCAL probes stay inside a window of SM_WINDOW slots that
-// starts where the key's smaller end lies in the table (lo slots / 2^nbits): neighbouring vertices then share cache lines of the
-// table, and the slot-ordered sweeps of k_sm_degree and k_sm_fill walk the vertices nearly in order.  A key that finds its
-// window taken (a vertex with many edges) goes on at a hashed place and from there slot by slot.  The sequence depends on the
-// key alone and no slot is ever emptied, so every thread that inserts a key meets the slot that holds it.  Against hashed places
-// alone the call takes 1 270 instead of 1 510 us at 256^3.
-constexpr unsigned long long SM_LOCAL = 32, SM_WINDOW = 32;
-__device__ __forceinline__ unsigned long long sm_slot(unsigned long long key, unsigned long long hk, unsigned long long probe,
-                                                      unsigned long long mask, int nbits) {
-#ifndef SFMX_SM_HASHED_ONLY  // diagnostic build for the A/B of DESIGN.md 21 (tools/bench_smooth.py --build-dir): hashed places only
-  if (probe < SM_LOCAL) return ((((key >> 32) * (mask + 1)) >> nbits) + ((hk + probe) & (SM_WINDOW - 1))) & mask;
-  probe -= SM_LOCAL;
-#endif
-  return ((hk >> 8) + probe) & mask;
-}
-
-__device__ __forceinline__ void sm_insert(int a, int b, unsigned long long* keys, int* uses, unsigned long long mask, int nbits) {
-  if (a == b) return;
-  const unsigned lo = (unsigned)min(a, b), hi = (unsigned)max(a, b);
-  const unsigned long long key = (unsigned long long)lo << 32 | hi;
-  const unsigned long long hk = sm_hash(key);
-  // a bounded number of probes: the table has more slots than there are edges, and no slot is ever emptied
-  for (unsigned long long probe = 0; probe <= mask + SM_LOCAL; probe++) {
-    const unsigned long long h = sm_slot(key, hk, probe, mask, nbits);
-    const unsigned long long cur = atomicCAS(&keys[h], SM_EMPTY, key);
-    if (cur == SM_EMPTY || cur == key) {
-      atomicAdd(&uses[2 * h + (a < b ? 0 : 1)], 1);
-      return;
-    }
-  }
-}
-
 __global__ __launch_bounds__(256) void k_sm_edges(const int* __restrict__ faces, int m, int n, unsigned long long* keys, int* uses,
                                                   unsigned long long mask, int nbits, int* __restrict__ counters) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= m) return;
-  const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  if ((unsigned)a >= (unsigned)n || (unsigned)b >= (unsigned)n || (unsigned)c >= (unsigned)n) {
-    counters[SM_FLAG] = 1;  // the call fails; nothing is accessed through the index
-    return;
-  }
-  sm_insert(a, b, keys, uses, mask, nbits);
-  sm_insert(b, c, keys, uses, mask, nbits);
-  sm_insert(c, a, keys, uses, mask, nbits);
-}
-
-// sums of K ints over the block into part[K * blockIdx.x ..]
-template <int K>
-__device__ __forceinline__ void sm_block_sums(int (&x)[K], int* __restrict__ part) {
-  __shared__ int red[4][K];
-#pragma unroll
-  for (int k = 0; k < K; k++)
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) x[k] += __shfl_xor(x[k], s, 64);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < K; k++) red[threadIdx.x >> 6][k] = x[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < K) part[K * blockIdx.x + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  et_insert_face(faces, f, n, keys, uses, mask, nbits, counters + SM_FLAG);
 }
 
 __global__ __launch_bounds__(256) void k_sm_degree(const unsigned long long* __restrict__ keys, const int* __restrict__ uses, size_t slots,
@@ -134,7 +70,7 @@ __global__ __launch_bounds__(256) void k_sm_degree(const unsigned long long* __r
   int c[3] = {0, 0, 0};  // edges, boundary, irregular
   for (size_t h = (size_t)blockIdx.x * 256 + threadIdx.x; h < slots; h += (size_t)gridDim.x * 256) {
     const unsigned long long key = keys[h];
-    if (key == SM_EMPTY) continue;
+    if (key == ET_EMPTY) continue;
     const unsigned lo = (unsigned)(key >> 32), hi = (unsigned)key;
     const int fwd = uses[2 * h], bwd = uses[2 * h + 1];
     atomicAdd(&cnt[lo], 1);
@@ -146,14 +82,14 @@ __global__ __launch_bounds__(256) void k_sm_degree(const unsigned long long* __r
     if (fwd + bwd == 1) c[1]++;
     else c[2]++;
   }
-  sm_block_sums<3>(c, counters + SM_EDGE_PART);
+  et_block_sums<3>(c, counters + SM_EDGE_PART);
 }
 
 __global__ __launch_bounds__(256) void k_sm_fill(const unsigned long long* __restrict__ keys, size_t slots, const int* __restrict__ row,
                                                  int* cursor, int* __restrict__ col) {
   for (size_t h = (size_t)blockIdx.x * 256 + threadIdx.x; h < slots; h += (size_t)gridDim.x * 256) {
     const unsigned long long key = keys[h];
-    if (key == SM_EMPTY) continue;
+    if (key == ET_EMPTY) continue;
     const unsigned lo = (unsigned)(key >> 32), hi = (unsigned)key;
     col[(size_t)row[lo] + (size_t)atomicAdd(&cursor[lo], 1)] = (int)hi;
     col[(size_t)row[hi] + (size_t)atomicAdd(&cursor[hi], 1)] = (int)lo;
@@ -211,7 +147,7 @@ __global__ __launch_bounds__(256) void k_sm_emit(const double* __restrict__ vert
       out[3 * v + k] = (iso || pnd) ? x : o[k] + ((double)Q[3 * v + k] * (1.0 / SM_SCALE)) * unit;
     }
   }
-  sm_block_sums<2>(c, counters + SM_VERT_PART);
+  et_block_sums<2>(c, counters + SM_VERT_PART);
 }
 
 }  // namespace
@@ -257,8 +193,7 @@ int sm_run(sfmx_ctx* ctx, sfmx_smooth* sm, const double* verts, int n, const int
   int* counters = reinterpret_cast<int*>(sm->work.as<char>() + b_work - SM_COUNTERS * 4);
   size_t slots = 0;
   if (m > 0) {
-    slots = 4;
-    while (slots < 4 * mm) slots <<= 1;  // at most 2^32
+    slots = et_slots(mm);
     SFMX_HIP(ctx, sm->table.ensure(slots * 16));
   }
   unsigned long long* keys = sm->table.as<unsigned long long>();
@@ -275,9 +210,7 @@ int sm_run(sfmx_ctx* ctx, sfmx_smooth* sm, const double* verts, int n, const int
   if (m > 0) {
     SFMX_HIP(ctx, hipMemsetAsync(keys, 0xFF, slots * 8, s));
     SFMX_HIP(ctx, hipMemsetAsync(uses, 0, slots * 8, s));
-    int nbits = 1;  // 2^nbits >= n
-    while ((1ll << nbits) < n) nbits++;
-    k_sm_edges<<<nbf, 256, 0, s>>>(faces, m, n, keys, uses, (unsigned long long)(slots - 1), nbits, counters);
+    k_sm_edges<<<nbf, 256, 0, s>>>(faces, m, n, keys, uses, (unsigned long long)(slots - 1), et_nbits(n), counters);
     if (n > 0) k_sm_degree<<<nbs, 256, 0, s>>>(keys, uses, slots, cnt, pinned, counters);
   }
   SFMX_HIP(ctx, hipGetLastError());

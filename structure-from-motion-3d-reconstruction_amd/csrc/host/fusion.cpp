@@ -87,6 +87,16 @@
 #pragma weak sfmx_smooth_counts
 #pragma weak sfmx_smooth_device_mesh
 #pragma weak sfmx_smooth_device_surface
+#pragma weak sfmx_smooth_run
+#pragma weak sfmx_fill_check_params
+#pragma weak sfmx_fill_create
+#pragma weak sfmx_fill_destroy
+#pragma weak sfmx_fill_fusion
+#pragma weak sfmx_fill_clean
+#pragma weak sfmx_fill_read
+#pragma weak sfmx_fill_counts
+#pragma weak sfmx_fill_device_mesh
+#pragma weak sfmx_fill_device_surface
 
 namespace {
 
@@ -102,7 +112,9 @@ struct Guard {
   sfmx_align* al = nullptr;
   sfmx_simplify* sm = nullptr;
   sfmx_smooth* ta = nullptr;
+  sfmx_fill* fl = nullptr;
   ~Guard() {
+    if (fl) sfmx_fill_destroy(ctx, fl);
     if (ta) sfmx_smooth_destroy(ctx, ta);
     if (sm) sfmx_simplify_destroy(ctx, sm);
     if (al) sfmx_align_destroy(ctx, al);
@@ -346,6 +358,19 @@ int sfmx_host_fusion_mesh_sm(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
                              const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
                              int32_t* smooth_counts, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_fl(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts, gt,
+                                  ev, render, align, simplify, simplify_counts, smooth, smooth_counts, nullptr, nullptr, res, ply_path, warn,
+                                  warn_cap);
+}
+
+int sfmx_host_fusion_mesh_fl(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, sfmx_fusion_result_ex* res,
+                             const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -367,6 +392,10 @@ int sfmx_host_fusion_mesh_sm(sfmx_ctx* ctx, const uint8_t* const* images, int on
   if (smooth && (!&sfmx_smooth_check_params || !&sfmx_smooth_create || !&sfmx_smooth_destroy || !&sfmx_smooth_fusion || !&sfmx_smooth_clean ||
                  !&sfmx_smooth_read || !&sfmx_smooth_counts || !&sfmx_smooth_device_mesh || !&sfmx_smooth_device_surface || !&sfmx_clean_read ||
                  !&sfmx_shade_vertices || !&sfmx_simplify_run || !sdist_linked()))
+    return SFMX_ERR_UNSUPPORTED;
+  if (fill && (!&sfmx_fill_check_params || !&sfmx_fill_create || !&sfmx_fill_destroy || !&sfmx_fill_fusion || !&sfmx_fill_clean ||
+               !&sfmx_fill_read || !&sfmx_fill_counts || !&sfmx_fill_device_mesh || !&sfmx_fill_device_surface || !&sfmx_smooth_run ||
+               !&sfmx_shade_vertices || !&sfmx_simplify_run || !sdist_linked()))
     return SFMX_ERR_UNSUPPORTED;
   int rc = sfmx_stereo_check_params(w, h, sp);
   if (rc != SFMX_OK) return rc;
@@ -410,6 +439,12 @@ int sfmx_host_fusion_mesh_sm(sfmx_ctx* ctx, const uint8_t* const* images, int on
     if (rc != SFMX_OK) return rc;
     if (smooth_counts)
       for (int q = 0; q < 5; q++) smooth_counts[q] = 0;
+  }
+  if (fill) {
+    rc = sfmx_fill_check_params(fill);
+    if (rc != SFMX_OK) return rc;
+    if (fill_counts)
+      for (int q = 0; q < 8; q++) fill_counts[q] = 0;
   }
   if (render) {
     if (render->n_cameras < 0 || (render->n_cameras > 0 && (!render->cameras || !render->out))) return SFMX_ERR_INVALID;
@@ -541,13 +576,51 @@ int sfmx_host_fusion_mesh_sm(sfmx_ctx* ctx, const uint8_t* const* images, int on
       clean_counts[3] = nf0 - nf;
     }
   }
+  // filling adds vertices and faces: the mesh that leaves it lies inside the fill object (fdv, fdn, fdf), and every later stage
+  // takes its faces and normals from there, not from the clean object or the extraction
+  const double *fdv = nullptr, *fdn = nullptr;
+  const int32_t* fdf = nullptr;
+  if (fill && nf > 0) {
+    if (!clean) {  // an uncleaned surface is extracted with its arrays so that it lies inside the volume object
+      std::vector<double> tv((size_t)nv * 3), tn(app ? (size_t)nv * 3 : 0);
+      std::vector<int32_t> tf((size_t)nf * 3);
+      rc = app ? sfmx_fusion_extract_normals(ctx, g.fu, tv.data(), nv, tf.data(), nf, tn.data(), &nv, &nf)
+               : sfmx_fusion_extract(ctx, g.fu, tv.data(), nv, tf.data(), nf, &nv, &nf);
+      if (rc != SFMX_OK) return rc;
+    }
+    rc = sfmx_fill_create(ctx, &g.fl);
+    if (rc == SFMX_OK) rc = clean ? sfmx_fill_clean(ctx, g.fl, g.cl, fill) : sfmx_fill_fusion(ctx, g.fl, g.fu, fill);
+    int counts[8] = {};
+    if (rc == SFMX_OK)
+      rc = sfmx_fill_counts(g.fl, &counts[0], &counts[1], &counts[2], &counts[3], &counts[4], &counts[5], &counts[6], &counts[7]);
+    if (rc == SFMX_OK && (sfmx_fill_device_mesh(g.fl, &fdv, &fdf, &nv, &nf) < 0 || nf <= 0)) rc = SFMX_ERR_INVALID;
+    if (rc == SFMX_OK && app) {
+      const double* tmp = nullptr;
+      if (sfmx_fill_device_surface(g.fl, &tmp, &fdn) != nv || !fdn) rc = SFMX_ERR_INVALID;
+    }
+    if (rc != SFMX_OK) return rc;
+    if (fill_counts)
+      for (int q = 0; q < 8; q++) fill_counts[q] = counts[q];
+  }
+  const bool filled = g.fl != nullptr;
   // smoothing moves vertices only: the faces and the normals of the mesh that leaves it are those of the stage before, on the
   // device (sdf, sdn) and, for an uncleaned surface, in the host arrays of the extraction that put it there (sv, sf, sn)
   std::vector<double> sv, sn;
   std::vector<int32_t> sf;
   const double *sdv = nullptr, *sdn = nullptr;
   const int32_t* sdf = nullptr;
-  if (smooth && nf > 0) {
+  if (smooth && nf > 0 && filled) {
+    rc = sfmx_smooth_create(ctx, &g.ta);
+    if (rc == SFMX_OK) rc = sfmx_smooth_run(ctx, g.ta, fdv, nv, fdf, nf, 1, smooth);
+    int counts[5] = {};
+    if (rc == SFMX_OK) rc = sfmx_smooth_counts(g.ta, &counts[0], &counts[1], &counts[2], &counts[3], &counts[4]);
+    int snf = 0;
+    if (rc == SFMX_OK && (sfmx_smooth_device_mesh(g.ta, &sdv, &sdf, &snf) != nv || snf != nf)) rc = SFMX_ERR_INVALID;
+    if (rc != SFMX_OK) return rc;
+    sdn = fdn;
+    if (smooth_counts)
+      for (int q = 0; q < 5; q++) smooth_counts[q] = counts[q];
+  } else if (smooth && nf > 0) {
     if (!clean) {
       sv.resize((size_t)nv * 3);
       sn.resize(app ? (size_t)nv * 3 : 0);
@@ -575,7 +648,7 @@ int sfmx_host_fusion_mesh_sm(sfmx_ctx* ctx, const uint8_t* const* images, int on
     // the cleaned surface lies inside the clean object; an uncleaned one is extracted with its arrays so that it lies inside
     // the volume object (the extraction always returns them to the host as well); a smoothed one lies inside the smooth object
     const int nv0 = nv, nf0 = nf;
-    if (!clean && !smoothed) {
+    if (!clean && !smoothed && !filled) {
       std::vector<double> tv((size_t)nv * 3), tn(app ? (size_t)nv * 3 : 0);
       std::vector<int32_t> tf((size_t)nf * 3);
       rc = app ? sfmx_fusion_extract_normals(ctx, g.fu, tv.data(), nv, tf.data(), nf, tn.data(), &nv, &nf)
@@ -585,6 +658,7 @@ int sfmx_host_fusion_mesh_sm(sfmx_ctx* ctx, const uint8_t* const* images, int on
     rc = sfmx_simplify_create(ctx, &g.sm);
     if (rc == SFMX_OK)
       rc = smoothed ? sfmx_simplify_run(ctx, g.sm, sdv, sdn, nv0, sdf, nf0, 1, simplify, &nv, &nf)
+           : filled ? sfmx_simplify_run(ctx, g.sm, fdv, fdn, nv0, fdf, nf0, 1, simplify, &nv, &nf)
            : clean  ? sfmx_simplify_clean(ctx, g.sm, g.cl, simplify, &nv, &nf)
                     : sfmx_simplify_fusion(ctx, g.sm, g.fu, simplify, &nv, &nf);
     int counts[3] = {};
@@ -620,13 +694,18 @@ int sfmx_host_fusion_mesh_sm(sfmx_ctx* ctx, const uint8_t* const* images, int on
       }
     } else if (smoothed) {
       rc = sfmx_smooth_read(ctx, g.ta, res->verts, nullptr);
-      if (rc == SFMX_OK && clean) rc = sfmx_clean_read(ctx, g.cl, nullptr, res->normals, res->faces, nullptr, nullptr, nullptr, nullptr);
-      if (rc == SFMX_OK && !clean) {
+      if (rc == SFMX_OK && filled) rc = sfmx_fill_read(ctx, g.fl, nullptr, res->normals, res->faces);
+      if (rc == SFMX_OK && !filled && clean) rc = sfmx_clean_read(ctx, g.cl, nullptr, res->normals, res->faces, nullptr, nullptr, nullptr, nullptr);
+      if (rc == SFMX_OK && !filled && !clean) {
         std::memcpy(res->faces, sf.data(), (size_t)nf * 3 * sizeof(int32_t));
         if (app) std::memcpy(res->normals, sn.data(), (size_t)nv * 3 * sizeof(double));
       }
       // the smoothed vertices are shaded with the normals they had
       if (rc == SFMX_OK && app) rc = sfmx_shade_vertices(ctx, g.sh, sdv, sdn, nv, 1, &ap, res->grey, res->views);
+    } else if (filled) {
+      rc = sfmx_fill_read(ctx, g.fl, res->verts, res->normals, res->faces);
+      // the filled vertices are shaded with the fill object's normals: a new vertex with the normal its loop gave it
+      if (rc == SFMX_OK && app) rc = sfmx_shade_vertices(ctx, g.sh, fdv, fdn, nv, 1, &ap, res->grey, res->views);
     } else if (clean) {
       rc = sfmx_clean_read(ctx, g.cl, res->verts, res->normals, res->faces, nullptr, nullptr, nullptr, nullptr);
       if (rc == SFMX_OK && app) {  // per vertex: the uncleaned shading gathered by vert_src
@@ -662,10 +741,13 @@ int sfmx_host_fusion_mesh_sm(sfmx_ctx* ctx, const uint8_t* const* images, int on
     rc = sfmx_sdist_create(ctx, &g.sd);
     if (rc == SFMX_OK && simplified && nf > 0 && (sfmx_simplify_device_mesh(g.sm, &mv, &mf, &mnf) != nv || mnf != nf))
       rc = SFMX_ERR_INVALID;
-    const bool own = simplified || smoothed;  // the final mesh is handed over as device pointers
+    const bool own = simplified || smoothed || filled;  // the final mesh is handed over as device pointers
     if (!simplified && smoothed) {
       mv = sdv;
       mf = sdf;
+    } else if (!simplified && filled) {
+      mv = fdv;
+      mf = fdf;
     }
     if (rc == SFMX_OK) rc = sfmx_sdist_set_target(ctx, g.sd, gt->verts, gt->n_verts, gt->faces, gt->n_faces, 0, &dp);
     if (rc == SFMX_OK && nf > 0) {

@@ -178,4 +178,23 @@ int sfmx_host_fusion_mesh_sm(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
                              const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
                              int32_t* smooth_counts, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_sm with the small holes of the surface filled by exact centroid fans between cleaning and
+// smoothing.  fill = NULL: exactly sfmx_host_fusion_mesh_sm (fill_counts is not touched).  Otherwise the order is: extract (with
+// normals when app is given) -> clean (when given) -> fill on the device (sfmx_fill_clean, or sfmx_fill_fusion without clean) ->
+// smooth (when given; sfmx_smooth_run on the fill object's device mesh) -> simplify (when given; sfmx_simplify_run) -> with app
+// the final device vertices are shaded -> with gt the final mesh is evaluated from where it lies on the device -> the result
+// arrays and the PLY are the final mesh.  After a fill the vertex count differs from the stage before, so every later stage takes
+// its faces and normals from the fill object.  fill->unit and origin are used as given (pipeline.fuse passes the voxel and the
+// volume's origin).  fill_counts (optional) int32 [8]: edges, boundary edges, irregular edges and complex vertices of the surface
+// that went in, the loops filled, their edges, and the new vertices and faces (zeros when the surface had no faces before the
+// stage).
+int sfmx_host_fusion_mesh_fl(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, sfmx_fusion_result_ex* res,
+                             const char* ply_path, char* warn, int warn_cap);
 }

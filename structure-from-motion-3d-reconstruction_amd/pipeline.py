@@ -185,6 +185,7 @@ CONSISTENCY_KEYS = ("rel_tol", "reproj_px", "min_support")
 CLEAN_KEYS = ("min_faces", "min_permille")
 SIMPLIFY_KEYS = ("factor", "cell", "origin")
 SMOOTH_KEYS = ("iters", "lam", "mu", "pin", "unit", "origin")
+FILL_KEYS = ("max_edges", "unit", "origin")
 EVALUATE_KEYS = ("gt_verts", "gt_faces", "d_max", "tau", "percentile", "cell")
 EVALUATION_FIELDS = ("accuracy", "acc_within", "acc_mean", "acc_max", "n_rec", "completeness", "comp_within", "n_gt")
 
@@ -272,7 +273,7 @@ def _split_fusion_params(params: dict):
 
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
-         consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, **params) -> dict:
+         consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, fill=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -312,7 +313,13 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     pairs of a lambda and a mu step over each vertex's distinct neighbours, with the vertices of every edge that is not used once in
     each direction held in place (pin=1).  unit (the length 2^20 fixed-point steps stand for) defaults to the voxel and origin to
     the volume's.  Normals stay with their vertices.  The dict gains smooth = dict(edges=, boundary_edges=, irregular_edges=,
-    pinned=, isolated=)."""
+    pinned=, isolated=).
+    fill: True, or dict(max_edges=32, unit=, origin=) -- the small holes of the surface (the cleaned one with clean) are filled on the
+    device by exact centroid fans before it is smoothed, simplified, shaded, evaluated and written: every closed loop
+    of at most `max_edges` boundary edges through simple vertices gets one new vertex at its rounded centroid (none for a loop of
+    three) and a fan of faces; the surface's outer rim and longer loops stay open.  unit and origin default as for smooth.  With
+    appearance a new vertex carries the normalised sum of its loop's normals and is shaded like any other.  The dict gains fill =
+    dict(edges=, boundary_edges=, irregular_edges=, complex_vertices=, filled_loops=, filled_edges=, new_verts=, new_faces=)."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -373,6 +380,14 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             raise TypeError(f"unknown smooth parameters {sorted(unknown)}")
         tp = capi.smooth_params(float(tkw.pop("unit", voxel)), origin=tkw.pop("origin", origin), **tkw)
         tcounts = np.zeros(5, np.int32)
+    hp = None
+    if fill:
+        hkw = {} if fill is True else dict(fill)
+        unknown = set(hkw) - set(FILL_KEYS)
+        if unknown:
+            raise TypeError(f"unknown fill parameters {sorted(unknown)}")
+        hp = capi.fill_params(float(hkw.pop("unit", voxel)), origin=hkw.pop("origin", origin), **hkw)
+        hcounts = np.zeros(8, np.int32)
     gt = None
     if evaluate is not None:
         ekw = dict(evaluate)
@@ -421,12 +436,24 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         seed = int(gkw.pop("seed", 1))
         aouts = (capi.AlignResult * max(len(pr), 1))()
         aq = AlignRequest(seed, capi.align_params(disp_min=fp.disp_min, **gkw), aouts)
-    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None:
+    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None or hp is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if tp is not None:
+        if hp is not None:
+            rc = lib.sfmx_host_fusion_mesh_fl(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None,
+                                              byref(rq) if rq is not None else None, byref(aq) if aq is not None else None,
+                                              byref(mp) if mp is not None else None,
+                                              mcounts.ctypes.data_as(POINTER(c_int)) if mp is not None else None,
+                                              byref(tp) if tp is not None else None,
+                                              tcounts.ctypes.data_as(POINTER(c_int)) if tp is not None else None,
+                                              byref(hp), hcounts.ctypes.data_as(POINTER(c_int)), *tail)
+        elif tp is not None:
             rc = lib.sfmx_host_fusion_mesh_sm(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -492,6 +519,8 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             out["simplify"] = dict(zip(("clusters", "degenerate", "duplicates", "verts_before", "faces_before"), (int(v) for v in mcounts)))
         if tp is not None:
             out["smooth"] = dict(zip(capi.SMOOTH_COUNTS, (int(v) for v in tcounts)))
+        if hp is not None:
+            out["fill"] = dict(zip(capi.FILL_COUNTS, (int(v) for v in hcounts)))
         if gt is not None:
             out["evaluation"] = ev.asdict()
         if rq is not None:
@@ -565,7 +594,8 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     dict, as fuse) removes the surface's small connected components; 'evaluate' (a dict, as fuse) evaluates the final mesh against
     a ground-truth mesh; 'render' (a dict, as fuse) ray casts the volume from further cameras; 'align' (True or a dict, as fuse) registers each later
     pair's view to the volume before it enters it; 'simplify' (True or a dict, as fuse) simplifies the final surface by exact vertex
-    clustering; 'smooth' (True or a dict, as fuse) smooths it with the exact Taubin filter first.  The run itself, its log and every other output are unchanged.
+    clustering; 'smooth' (True or a dict, as fuse) smooths it with the exact Taubin filter first; 'fill' (True or a dict, as fuse) fills its small
+    holes before that.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -634,9 +664,10 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         align = fz.pop("align", False)
         simplify = fz.pop("simplify", False)
         smooth = fz.pop("smooth", False)
+        fill = fz.pop("fill", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
                                  appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align,
-                                 simplify=simplify, smooth=smooth, **fz)
+                                 simplify=simplify, smooth=smooth, fill=fill, **fz)
     return out
 
 

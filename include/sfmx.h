@@ -797,6 +797,66 @@ int sfmx_fill_device_surface(const sfmx_fill* fl, const double** verts, const do
 /* device time (us) from the first to the last launch of the last run when timing is on (sfmx_set_timing), else 0 */
 double sfmx_fill_last_us(const sfmx_fill* fl);
 
+/* ---- rendering a triangle mesh from any camera: an exact z-buffer ------------------------------------------- */
+/* Per vertex X: p = X - c, q_r = (R_rw[r][0] p0 + R_rw[r][1] p1) + R_rw[r][2] p2; near iff q2 >= z_min; u = (f q0) / q2 + cx,
+ * v = (f q1) / q2 + cy; inband iff near and |u|, |v| <= 16384; U = (int64)floor(u 256 + 0.5), V likewise; r = 1 / q2.  Pixel
+ * (x, y) is the point (256 x, 256 y).
+ * Per face, in this order: an index outside [0, n) fails the call; a vertex that is not near: faces_behind (there is NO
+ * near-plane clipping: such a face is dropped whole); a vertex that is not inband: faces_outside; A = (U1 - U0)(V2 - V0) -
+ * (V1 - V0)(U2 - U0) == 0: faces_degenerate; the face is back-facing iff A > 0 (the image's y points down), counted in faces_back
+ * before culling; cull = 1 drops back faces and cull = 2 front faces (faces_culled).
+ * Coverage: with sg = sign(A) and, for vertex i, j = i + 1 mod 3, k = i + 2 mod 3: dx = sg (U_k - U_j), dy = sg (V_k - V_j),
+ * e_i(x, y) = dx (256 y - V_j) - dy (256 x - U_j) in int64.  Pixel (x, y) of the image is covered iff for every i e_i > 0, or
+ * e_i == 0 and (dy < 0 or (dy == 0 and dx > 0)) (the top-left rule: of two faces that share an edge exactly one owns a centre on
+ * it).  A covered (face, pixel) pair is a fragment; faces_drawn counts the faces with at least one.
+ * Depth of a fragment: s = ((double)e0 r0 + (double)e1 r1) + (double)e2 r2, depth = (double)|A| / s.  The pixel's winner is the
+ * fragment with the smallest key (bits((float)depth) << 32) | face: depths are compared after rounding to float and equal ones go
+ * to the smaller face index.
+ * Per pixel with a winner, recomputed in double from the winning face: depth; point = c + depth dw with dw as in the ray
+ * casting above; t_i = (double)e_i r_i; N = cross(X1 - X0, X2 - X0), or with normals N_a = (t0 n0a + t1 n1a) + t2 n2a;
+ * normal = N / len or 0 unless len > 0; shaded = the ray casting's head light; with grey, g = ((t0 g0 + t1 g1) + t2 g2) / s and
+ * grey = min(255, floor(g + 0.5)).  A pixel without one has face -1, depth 0, a zero point and normal and shaded = grey =
+ * background.  hits counts the pixels with a winner, back_pixels those whose winner is back-facing.
+ * Coverage and the counts are integers, a key depends on (face, pixel) alone and a minimum on no order, so every output is
+ * bit-identical to the NumPy restatement in tests/raster_ref.py whatever the schedule.
+ * The camera is a sfmx_fusion_view: R_rw, c_left, f (> 0), cx, cy, w, h are used, B is ignored.  w <= 4096, w * h <= 2^24. */
+#define SFMX_RASTER_MAX_PIXELS (1 << 24) /* w * h */
+#define SFMX_RASTER_MAX_VERTS (1 << 24)  /* n < this */
+#define SFMX_RASTER_MAX_FACES (1 << 30)  /* m < this */
+typedef struct sfmx_raster sfmx_raster;  /* the device outputs of the last run and the work buffers; they grow on demand and are kept */
+typedef struct sfmx_raster_params {
+  double z_min;       /* a vertex nearer than this drops its faces; finite, > 0; no default */
+  int cull;           /* 0 = none (default), 1 = drop back faces, 2 = drop front faces */
+  uint8_t background; /* shaded and grey of a pixel without a winner (default 0) */
+} sfmx_raster_params;
+void sfmx_raster_default_params(sfmx_raster_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_raster_check_params(const sfmx_raster_params* p);
+int sfmx_raster_create(sfmx_ctx* ctx, sfmx_raster** out);
+void sfmx_raster_destroy(sfmx_ctx* ctx, sfmx_raster* rs);
+/* verts double [n][3], normals double [n][3] or NULL, grey u8 [n] or NULL, faces int32 [m][3]; host pointers (copied into the
+ * object) or (on_device = 1) device pointers (read in place; they must stay until the call returns); 0 <= n < 2^24,
+ * 0 <= m < 2^30.  A face index outside [0, n) is found on the device without any access through it and gives SFMX_ERR_INVALID;
+ * the object stays usable.  A failed call leaves no result.  A render that hits nothing (m = 0 included) is not an error.
+ * The device meshes of the fusion, clean, fill, smooth and simplify objects are fed from their _device_mesh / _device_surface
+ * getters with on_device = 1. */
+int sfmx_raster_run(sfmx_ctx* ctx, sfmx_raster* rs, const double* verts, const double* normals, const uint8_t* grey, int n,
+                    const int32_t* faces, int m, int on_device, const sfmx_fusion_view* view, const sfmx_raster_params* p);
+/* the last run to the host: depth double [h][w], face int32 [h][w], points / normals double [h][w][3], shaded / grey u8 [h][w];
+ * any may be NULL.  SFMX_ERR_INVALID before a run, and for grey after a run without grey. */
+int sfmx_raster_read(sfmx_ctx* ctx, sfmx_raster* rs, double* depth, int32_t* face, double* points, double* normals, uint8_t* shaded,
+                     uint8_t* grey);
+/* of the last run: counts8 int32 [8] = faces_behind, faces_outside, faces_degenerate, faces_back, faces_culled, faces_drawn, hits,
+ * back_pixels, and *fragments; either may be NULL.  SFMX_ERR_INVALID (and zeros) before a run; needs no context. */
+int sfmx_raster_counts(const sfmx_raster* rs, int32_t* counts8, uint64_t* fragments);
+/* the points and normals of all w * h pixels of the last run on the device (for sfmx_shade_vertices with on_device = 1);
+ * *n = w * h.  SFMX_ERR_INVALID (and NULLs, 0) before a run; needs no context.  Valid until the next run on rs. */
+int sfmx_raster_device_surface(const sfmx_raster* rs, const double** points, const double** normals, int* n);
+/* device time (us) from the first to the last launch of the last run when timing is on (sfmx_set_timing), else 0 */
+double sfmx_raster_last_us(const sfmx_raster* rs);
+/* faces of the last run whose box of pixel centres went to the tiled path (a property of the schedule, not of the result) */
+int sfmx_raster_last_big_faces(const sfmx_raster* rs);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

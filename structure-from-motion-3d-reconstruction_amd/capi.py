@@ -61,6 +61,8 @@ SYMBOLS = [
     "sfmx_fill_default_params", "sfmx_fill_check_params", "sfmx_fill_create", "sfmx_fill_destroy", "sfmx_fill_run",
     "sfmx_fill_fusion", "sfmx_fill_clean", "sfmx_fill_read", "sfmx_fill_sizes", "sfmx_fill_counts",
     "sfmx_fill_device_mesh", "sfmx_fill_device_surface", "sfmx_fill_last_us",
+    "sfmx_raster_default_params", "sfmx_raster_check_params", "sfmx_raster_create", "sfmx_raster_destroy", "sfmx_raster_run",
+    "sfmx_raster_read", "sfmx_raster_counts", "sfmx_raster_device_surface", "sfmx_raster_last_us", "sfmx_raster_last_big_faces",
 ]
 
 
@@ -373,6 +375,40 @@ def raycast_check_params(**kw) -> bool:
     return load_library().sfmx_raycast_check_params(byref(raycast_params(**kw))) == SFMX_OK
 
 
+class RasterParams(ctypes.Structure):
+    _fields_ = [("z_min", c_double), ("cull", c_int), ("background", c_uint8)]
+
+
+# z_min has no default (a depth in the mesh's units)
+RASTER_DEFAULTS = dict(cull=0, background=0)
+RASTER_COUNTS = ("faces_behind", "faces_outside", "faces_degenerate", "faces_back", "faces_culled", "faces_drawn", "hits", "back_pixels")
+RASTER_MAX_PIXELS, RASTER_MAX_VERTS, RASTER_MAX_FACES = 1 << 24, 1 << 24, 1 << 30  # SFMX_RASTER_MAX_*
+
+
+def raster_params(z_min=0.0, **kw) -> RasterParams:
+    unknown = set(kw) - set(RASTER_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown raster parameters {sorted(unknown)}")
+    kw = {**RASTER_DEFAULTS, **kw}
+    if int(kw["cull"]) != kw["cull"]:
+        raise TypeError("raster parameter cull is an integer")
+    if not 0 <= int(kw["background"]) <= 255:
+        raise ValueError(f"background = {kw['background']} is not a byte")
+    return RasterParams(float(z_min), int(kw["cull"]), int(kw["background"]))
+
+
+def raster_default_params() -> dict:
+    """sfmx_raster_default_params as a dict (needs no device)"""
+    p = RasterParams()
+    load_library().sfmx_raster_default_params(byref(p))
+    return dict(z_min=p.z_min, cull=p.cull, background=p.background)
+
+
+def raster_check_params(z_min=0.0, **kw) -> bool:
+    """True if sfmx_raster_run would accept the parameters; needs no device"""
+    return load_library().sfmx_raster_check_params(byref(raster_params(z_min, **kw))) == SFMX_OK
+
+
 ALIGN_ITERS_CAP = 64  # SFMX_ALIGN_ITERS_CAP
 ALIGN_CONVERGED, ALIGN_MAX_ITERS, ALIGN_TOO_FEW, ALIGN_DEGENERATE = range(4)
 ALIGN_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")
@@ -460,6 +496,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_simplify_last_us.restype = c_double
         _lib.sfmx_smooth_last_us.restype = c_double
         _lib.sfmx_fill_last_us.restype = c_double
+        _lib.sfmx_raster_last_us.restype = c_double
     return _lib
 
 
@@ -1291,6 +1328,104 @@ class Raycast:
             pass
 
 
+class Raster:
+    """sfmx_raster: the visible face, depth, point, normal, head-light shade and interpolated grey per pixel of a pinhole camera,
+    from an exact z-buffer over a triangle mesh.  The device buffers grow on demand and are kept between runs."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.shape = None  # (h, w) of the last render
+        self.has_grey = False
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_raster_create(ctx.h_, byref(self.h_)))
+
+    def render(self, verts, faces, cam: dict, z_min, normals=None, grey=None, n=None, m=None, w=None, h=None, read=True, **params):
+        """verts float64 [n][3], faces int32 [m][3], normals float64 [n][3] or None, grey uint8 [n] or None: numpy arrays, or ints
+        (device pointers, read in place) with n= and m= given.  cam: dict(R_rw, c_left, f, cx, cy, w, h) (B is not used; w= / h=
+        override the dict's image size).  params: RASTER_DEFAULTS keys.  Returns read()'s dict, or None with read=False."""
+        p = raster_params(z_min, **params)
+        w, h = int(cam["w"] if w is None else w), int(cam["h"] if h is None else h)
+        v = fusion_view({**cam, "B": cam.get("B", 0.0)}, w, h)
+        on_dev = isinstance(verts, int)
+        if on_dev:
+            if not isinstance(faces, int) or any(a is not None and not isinstance(a, int) for a in (normals, grey)):
+                raise TypeError("verts, faces, normals and grey: all host arrays or all device pointers")
+            pv, pf = c_void_p(verts), c_void_p(faces)
+            pn, pg = c_void_p(normals), c_void_p(grey)
+            n, m = int(n), int(m)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            n, m = len(verts), len(faces)
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+            pn = pg = None
+            if normals is not None:
+                normals = _f64(normals).reshape(-1, 3)
+                assert len(normals) == n
+                pn = normals.ctypes.data_as(c_void_p)
+            if grey is not None:
+                grey = np.ascontiguousarray(grey, np.uint8).reshape(-1)
+                assert len(grey) == n
+                pg = grey.ctypes.data_as(c_void_p)
+        self.shape = None  # only now: a call refused above, in Python, leaves the library's result and its shape alone
+        self.ctx._chk(self.ctx.lib.sfmx_raster_run(self.ctx.h_, self.h_, pv, pn, pg, c_int(n), pf, c_int(m), c_int(1 if on_dev else 0),
+                                                   byref(v), byref(p)))
+        self.shape, self.has_grey = (h, w), grey is not None
+        return self.read() if read else None
+
+    def read(self) -> dict:
+        """the last render: dict(depth f64 [h][w], face int32 [h][w], points / normals f64 [h][w][3], shaded u8 [h][w], grey u8
+        [h][w] when the run had grey, the RASTER_COUNTS and fragments)"""
+        if self.shape is None:  # no render: the library says so, and copies nothing
+            self.ctx._chk(self.ctx.lib.sfmx_raster_read(self.ctx.h_, self.h_, None, None, None, None, None, None))
+            raise SfmxError(SFMX_ERR_INVALID, "sfmx_raster_read: no render made through this object")
+        h, w = self.shape
+        depth, face = np.zeros((h, w)), np.zeros((h, w), np.int32)
+        points, normals = np.zeros((h, w, 3)), np.zeros((h, w, 3))
+        shaded = np.zeros((h, w), np.uint8)
+        grey = np.zeros((h, w), np.uint8) if self.has_grey else None
+        self.ctx._chk(self.ctx.lib.sfmx_raster_read(self.ctx.h_, self.h_, _p(depth, c_double), _p(face, c_int32), _p(points, c_double),
+                                                    _p(normals, c_double), _p(shaded, c_uint8), _p(grey, c_uint8) if self.has_grey else None))
+        out = dict(depth=depth, face=face, points=points, normals=normals, shaded=shaded, **self.counts())
+        if self.has_grey:
+            out["grey"] = grey
+        return out
+
+    def counts(self) -> dict:
+        """the RASTER_COUNTS and fragments of the last render; raises before one"""
+        c, fr = (c_int32 * 8)(), c_uint64(0)
+        rc = self.ctx.lib.sfmx_raster_counts(self.h_, c, byref(fr))
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_raster_counts: no render")
+        return dict(zip(RASTER_COUNTS, (int(x) for x in c)), fragments=int(fr.value))
+
+    def device_surface(self):
+        """(n = w * h, device pointer of the points, of the normals) of the last render; raises before one"""
+        pts, nrm, n = c_void_p(), c_void_p(), c_int(0)
+        rc = self.ctx.lib.sfmx_raster_device_surface(self.h_, byref(pts), byref(nrm), byref(n))
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_raster_device_surface: no render")
+        return n.value, pts.value, nrm.value
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_raster_last_us(self.h_))
+
+    def last_big_faces(self) -> int:
+        """faces of the last render that went to the tiled path"""
+        return int(self.ctx.lib.sfmx_raster_last_big_faces(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_raster_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Align:
     """sfmx_align: registration of a view to a TSDF volume by direct Gauss-Newton alignment.  The device work
     buffers grow on demand and are kept between calls."""
@@ -1734,6 +1869,9 @@ class Context:
 
     def align(self) -> "Align":
         return Align(self)
+
+    def raster(self) -> "Raster":
+        return Raster(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

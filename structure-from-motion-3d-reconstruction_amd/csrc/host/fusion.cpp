@@ -97,6 +97,12 @@
 #pragma weak sfmx_fill_counts
 #pragma weak sfmx_fill_device_mesh
 #pragma weak sfmx_fill_device_surface
+#pragma weak sfmx_raster_check_params
+#pragma weak sfmx_raster_create
+#pragma weak sfmx_raster_destroy
+#pragma weak sfmx_raster_run
+#pragma weak sfmx_raster_read
+#pragma weak sfmx_raster_counts
 
 namespace {
 
@@ -113,7 +119,9 @@ struct Guard {
   sfmx_simplify* sm = nullptr;
   sfmx_smooth* ta = nullptr;
   sfmx_fill* fl = nullptr;
+  sfmx_raster* rs = nullptr;
   ~Guard() {
+    if (rs) sfmx_raster_destroy(ctx, rs);
     if (fl) sfmx_fill_destroy(ctx, fl);
     if (ta) sfmx_smooth_destroy(ctx, ta);
     if (sm) sfmx_simplify_destroy(ctx, sm);
@@ -371,6 +379,19 @@ int sfmx_host_fusion_mesh_fl(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, sfmx_fusion_result_ex* res,
                              const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_rs(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts, gt,
+                                  ev, render, align, simplify, simplify_counts, smooth, smooth_counts, fill, fill_counts, nullptr, res, ply_path,
+                                  warn, warn_cap);
+}
+
+int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -396,6 +417,9 @@ int sfmx_host_fusion_mesh_fl(sfmx_ctx* ctx, const uint8_t* const* images, int on
   if (fill && (!&sfmx_fill_check_params || !&sfmx_fill_create || !&sfmx_fill_destroy || !&sfmx_fill_fusion || !&sfmx_fill_clean ||
                !&sfmx_fill_read || !&sfmx_fill_counts || !&sfmx_fill_device_mesh || !&sfmx_fill_device_surface || !&sfmx_smooth_run ||
                !&sfmx_shade_vertices || !&sfmx_simplify_run || !sdist_linked()))
+    return SFMX_ERR_UNSUPPORTED;
+  if (raster && (!&sfmx_raster_check_params || !&sfmx_raster_create || !&sfmx_raster_destroy || !&sfmx_raster_run || !&sfmx_raster_read ||
+                 !&sfmx_raster_counts))
     return SFMX_ERR_UNSUPPORTED;
   int rc = sfmx_stereo_check_params(w, h, sp);
   if (rc != SFMX_OK) return rc;
@@ -451,6 +475,15 @@ int sfmx_host_fusion_mesh_fl(sfmx_ctx* ctx, const uint8_t* const* images, int on
     rc = sfmx_raycast_check_params(&render->params);
     if (rc != SFMX_OK) return rc;
     for (int q = 0; q < render->n_cameras; q++) render->out[q].hits = 0;
+  }
+  if (raster) {
+    if (raster->n_cameras < 0 || (raster->n_cameras > 0 && (!raster->cameras || !raster->out))) return SFMX_ERR_INVALID;
+    rc = sfmx_raster_check_params(&raster->params);
+    if (rc != SFMX_OK) return rc;
+    for (int q = 0; q < raster->n_cameras; q++) {
+      for (int32_t& c : raster->out[q].counts) c = 0;
+      raster->out[q].fragments = 0;
+    }
   }
   if (align) {
     // the filter needs every pose before anything is integrated
@@ -786,6 +819,30 @@ int sfmx_host_fusion_mesh_fl(sfmx_ctx* ctx, const uint8_t* const* images, int on
       rc = sfmx_raycast_render(ctx, g.rc, g.fu, &render->cameras[q], &render->params);
       if (rc == SFMX_OK) rc = sfmx_raycast_read(ctx, g.rc, o.depth, o.normals, o.points, o.shaded, &o.hits);
       if (rc == SFMX_OK && app && (o.grey || o.views)) rc = sfmx_raycast_shade(ctx, g.rc, g.sh, &ap, o.grey, o.views);
+    }
+    if (rc != SFMX_OK) {
+      const int keep = res->n_views;
+      sfmx_host_fusion_free_ex(res);
+      res->n_views = keep;
+      if (gt) *ev = sfmx_surface_eval_result{};
+      return rc;
+    }
+  }
+  if (raster && raster->n_cameras > 0) {
+    // the final mesh, the one in the result arrays and the PLY, with the appearance normals and grey when they were made.  The
+    // grey exists on the host only (the shade stage returns it there) and a run takes its arrays from one side, so the mesh is
+    // fed from the result arrays: the same bytes as the device copy the last stage left.  A surface without faces renders the
+    // background.
+    rc = sfmx_raster_create(ctx, &g.rs);
+    for (int q = 0; rc == SFMX_OK && q < raster->n_cameras; q++) {
+      sfmx_raster_out& o = raster->out[q];
+      const bool attrs = app && nf > 0;  // a surface without faces has no appearance arrays: its grey image is the background
+      rc = sfmx_raster_run(ctx, g.rs, res->verts, attrs ? res->normals : nullptr, attrs ? res->grey : nullptr, res->n_verts, res->faces,
+                           res->n_faces, 0, &raster->cameras[q], &raster->params);
+      if (rc == SFMX_OK) rc = sfmx_raster_read(ctx, g.rs, o.depth, o.face, o.points, o.normals, o.shaded, attrs ? o.grey : nullptr);
+      if (rc == SFMX_OK && app && !attrs && o.grey)
+        std::memset(o.grey, raster->params.background, (size_t)raster->cameras[q].w * (size_t)raster->cameras[q].h);
+      if (rc == SFMX_OK) rc = sfmx_raster_counts(g.rs, o.counts, &o.fragments);
     }
     if (rc != SFMX_OK) {
       const int keep = res->n_views;

@@ -197,4 +197,36 @@ int sfmx_host_fusion_mesh_fl(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, sfmx_fusion_result_ex* res,
                              const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_fl with the final mesh rendered from further cameras by the exact z-buffer.  raster = NULL:
+// exactly sfmx_host_fusion_mesh_fl.  Otherwise, after every other stage, each camera (R_rw, c_left, f, cx, cy, w, h of a
+// sfmx_fusion_view; B is not used) renders the mesh that goes into the result arrays and the PLY (a surface without faces renders
+// the background), with the appearance normals and grey per vertex when app is given, and the arrays of out[i] that are not NULL
+// are filled (caller allocated: depth double [h][w], face int32 [h][w], points / normals double [h][w][3], shaded u8 [h][w], and
+// with app grey u8 [h][w]; without app grey is left alone).  counts and fragments are sfmx_raster_counts'.  The mesh, the PLY,
+// the ray-cast renders and every other output are what they are without raster.
+struct sfmx_raster_out {
+  double* depth;
+  int32_t* face;
+  double* points;
+  double* normals;
+  uint8_t* shaded;
+  uint8_t* grey;
+  int32_t counts[8];
+  uint64_t fragments;
+};
+struct sfmx_raster_request {
+  const sfmx_fusion_view* cameras;
+  int n_cameras;
+  sfmx_raster_params params;
+  sfmx_raster_out* out;  // [n_cameras]
+};
+int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
 }

@@ -214,6 +214,18 @@ class RenderRequest(ctypes.Structure):
     _fields_ = [("cameras", POINTER(capi.FusionView)), ("n_cameras", c_int), ("params", capi.RaycastParams), ("out", POINTER(RenderOut))]
 
 
+RASTER_KEYS = ("cameras", "w", "h", "z_min", "cull", "background", "pgm_prefix")
+
+
+class RasterOut(ctypes.Structure):
+    _fields_ = [("depth", POINTER(c_double)), ("face", POINTER(c_int)), ("points", POINTER(c_double)), ("normals", POINTER(c_double)),
+                ("shaded", POINTER(c_ubyte)), ("grey", POINTER(c_ubyte)), ("counts", c_int * 8), ("fragments", ctypes.c_uint64)]
+
+
+class RasterRequest(ctypes.Structure):
+    _fields_ = [("cameras", POINTER(capi.FusionView)), ("n_cameras", c_int), ("params", capi.RasterParams), ("out", POINTER(RasterOut))]
+
+
 ALIGN_KEYS = ("seed", "max_iters", "stride", "min_pixels", "damping", "eps_rot", "eps_trans", "min_weight")
 
 
@@ -273,7 +285,8 @@ def _split_fusion_params(params: dict):
 
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
-         consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, fill=False, **params) -> dict:
+         consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, fill=False, raster=None,
+         **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -319,7 +332,12 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     of at most `max_edges` boundary edges through simple vertices gets one new vertex at its rounded centroid (none for a loop of
     three) and a fan of faces; the surface's outer rim and longer loops stay open.  unit and origin default as for smooth.  With
     appearance a new vertex carries the normalised sum of its loop's normals and is shaded like any other.  The dict gains fill =
-    dict(edges=, boundary_edges=, irregular_edges=, complex_vertices=, filled_loops=, filled_edges=, new_verts=, new_faces=)."""
+    dict(edges=, boundary_edges=, irregular_edges=, complex_vertices=, filled_loops=, filled_edges=, new_verts=, new_faces=).
+    raster: dict(cameras=[dict(R_rw, c_left, f, cx, cy), ...], w=, h=, z_min=, cull=0, background=0, pgm_prefix=None) -- the final
+    mesh, the one in the arrays and the PLY, is rendered from each camera at w x h by the exact z-buffer (z_min is
+    required): the dict gains rasters = [dict(depth, face, points, normals, shaded, the capi.RASTER_COUNTS, fragments), ...]; with
+    appearance the vertex normals and grey are interpolated and each also carries grey.  pgm_prefix writes
+    <prefix>_<i>_mesh_shaded.pgm (and _mesh_grey.pgm with appearance).  Everything else is what it is without raster."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -427,6 +445,31 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             for a in rarr])
         rq = RenderRequest(rviews, len(rcams), capi.raycast_params(rkw["z_min"], rkw["z_max"], rkw.get("step", 0.0), rkw.get("min_weight", 0),
                                                                    rkw.get("background", 0)), routs)
+    zq = None
+    if raster is not None:
+        zkw = dict(raster)
+        unknown = set(zkw) - set(RASTER_KEYS)
+        if unknown:
+            raise TypeError(f"unknown raster parameters {sorted(unknown)}")
+        missing = [k for k in ("cameras", "w", "h", "z_min") if k not in zkw]
+        if missing:
+            raise TypeError(f"raster needs {missing}")
+        zw, zh = int(zkw["w"]), int(zkw["h"])
+        if zw < 1 or zh < 1 or zw > 4096 or zw * zh > capi.RASTER_MAX_PIXELS:
+            raise ValueError(f"raster size {zw} x {zh} is outside 1 <= w <= 4096, w * h <= 2^24")
+        zcams = list(zkw["cameras"])
+        zviews = (capi.FusionView * max(len(zcams), 1))(*[capi.fusion_view({**c, "B": c.get("B", 0.0)}, zw, zh) for c in zcams])
+        zarr = [dict(depth=np.zeros((zh, zw)), face=np.zeros((zh, zw), np.int32), points=np.zeros((zh, zw, 3)), normals=np.zeros((zh, zw, 3)),
+                     shaded=np.zeros((zh, zw), np.uint8)) for _ in zcams]
+        if ap is not None:
+            for a in zarr:
+                a.update(grey=np.zeros((zh, zw), np.uint8))
+        zouts = (RasterOut * max(len(zcams), 1))(*[
+            RasterOut(a["depth"].ctypes.data_as(dp), a["face"].ctypes.data_as(POINTER(c_int)), a["points"].ctypes.data_as(dp),
+                      a["normals"].ctypes.data_as(dp), a["shaded"].ctypes.data_as(POINTER(c_ubyte)),
+                      a["grey"].ctypes.data_as(POINTER(c_ubyte)) if ap is not None else None) for a in zarr])
+        zq = RasterRequest(zviews, len(zcams), capi.raster_params(zkw["z_min"], cull=zkw.get("cull", 0), background=zkw.get("background", 0)),
+                           zouts)
     aq = None
     if align:
         gkw = {} if align is True else dict(align)
@@ -436,12 +479,25 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         seed = int(gkw.pop("seed", 1))
         aouts = (capi.AlignResult * max(len(pr), 1))()
         aq = AlignRequest(seed, capi.align_params(disp_min=fp.disp_min, **gkw), aouts)
-    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None or hp is not None:
+    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None or hp is not None or zq is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if hp is not None:
+        if zq is not None:
+            rc = lib.sfmx_host_fusion_mesh_rs(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None,
+                                              byref(rq) if rq is not None else None, byref(aq) if aq is not None else None,
+                                              byref(mp) if mp is not None else None,
+                                              mcounts.ctypes.data_as(POINTER(c_int)) if mp is not None else None,
+                                              byref(tp) if tp is not None else None,
+                                              tcounts.ctypes.data_as(POINTER(c_int)) if tp is not None else None,
+                                              byref(hp) if hp is not None else None,
+                                              hcounts.ctypes.data_as(POINTER(c_int)) if hp is not None else None, byref(zq), *tail)
+        elif hp is not None:
             rc = lib.sfmx_host_fusion_mesh_fl(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -530,6 +586,14 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                     write_pgm(f"{rkw['pgm_prefix']}_{i}_shaded.pgm", a["shaded"])
                     if ap is not None:
                         write_pgm(f"{rkw['pgm_prefix']}_{i}_grey.pgm", a["grey"])
+        if zq is not None:
+            out["rasters"] = [dict(a, **dict(zip(capi.RASTER_COUNTS, (int(c) for c in zouts[i].counts))), fragments=int(zouts[i].fragments))
+                              for i, a in enumerate(zarr)]
+            if zkw.get("pgm_prefix"):
+                for i, a in enumerate(zarr):
+                    write_pgm(f"{zkw['pgm_prefix']}_{i}_mesh_shaded.pgm", a["shaded"])
+                    if ap is not None:
+                        write_pgm(f"{zkw['pgm_prefix']}_{i}_mesh_grey.pgm", a["grey"])
         if aq is not None:
             out["alignment"] = []
             for q in range(len(pr)):
@@ -595,7 +659,7 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     a ground-truth mesh; 'render' (a dict, as fuse) ray casts the volume from further cameras; 'align' (True or a dict, as fuse) registers each later
     pair's view to the volume before it enters it; 'simplify' (True or a dict, as fuse) simplifies the final surface by exact vertex
     clustering; 'smooth' (True or a dict, as fuse) smooths it with the exact Taubin filter first; 'fill' (True or a dict, as fuse) fills its small
-    holes before that.  The run itself, its log and every other output are unchanged.
+    holes before that; 'raster' (a dict, as fuse) renders the final mesh from further cameras.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -665,9 +729,10 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         simplify = fz.pop("simplify", False)
         smooth = fz.pop("smooth", False)
         fill = fz.pop("fill", False)
+        raster = fz.pop("raster", None)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
                                  appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align,
-                                 simplify=simplify, smooth=smooth, fill=fill, **fz)
+                                 simplify=simplify, smooth=smooth, fill=fill, raster=raster, **fz)
     return out
 
 

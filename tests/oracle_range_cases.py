@@ -230,9 +230,16 @@ def _tracker_cases():
 
 # ---- dense solve ----------------------------------------------------------------------------------------------------------------
 def _solve_run(A, b):
+    """A, b: one system, or tuples of several (the sweep of solve_inputs: one case per n) -> rc and x of each under its name"""
     def run(lib, pre):
-        rc, x = H.solve_gauss(lib, pre, A, b)
-        return {"rc": rc, "x": x if rc == 0 else np.zeros(0)}
+        if not isinstance(A, tuple):
+            rc, x = H.solve_gauss(lib, pre, A, b)
+            return {"rc": rc, "x": x if rc == 0 else np.zeros(0)}
+        res = {}
+        for name, Ak, bk in zip(SI.SWEEP_SYSTEMS, A, b):
+            rc, x = H.solve_gauss(lib, pre, Ak, bk)
+            res[f"{name}/rc"], res[f"{name}/x"] = rc, x if rc == 0 else np.zeros(0)
+        return res
     return run
 
 

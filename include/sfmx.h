@@ -857,6 +857,83 @@ double sfmx_raster_last_us(const sfmx_raster* rs);
 /* faces of the last run whose box of pixel centres went to the tiled path (a property of the schedule, not of the result) */
 int sfmx_raster_last_big_faces(const sfmx_raster* rs);
 
+/* ---- which faces and vertices a set of cameras sees: exact multi-view visibility ----------------------------- */
+/* The object holds an ordered list of V >= 0 views, each a sfmx_fusion_view under the z-buffer's camera rules above (B ignored,
+ * sizes may differ), and optionally one image u8 [h][w] per view; a run needs an image on every view or on none.
+ * Per view k: the key image of the whole mesh at cull = 0 (back faces occlude too), exactly as sfmx_raster_run builds it.
+ * Vertex i is visible in view k iff it is inband, its pixel x = (U + 128) >> 8, y = (V + 128) >> 8 lies in the image, and that
+ * pixel's key is empty or q2 <= D + depth_tol, with q2 the vertex's depth and D = (double)(float) of the key's high word: one
+ * double addition and one comparison, false for a NaN.  vert_views[i] counts such views.
+ * Face f in view k, with A the z-buffer's integer area from the snapped corners: seen iff its three vertices are visible and
+ * A < 0; seen from behind iff they are and A > 0; neither with A == 0 or a corner that is not visible.  face_views[f] and
+ * face_back_views[f] count these views.
+ * Face f is kept iff face_views[f] >= min_views (0 keeps everything and only measures).  The output is as sfmx_clean gives it:
+ * kept faces in input order, the vertices a kept face uses in ascending input index with their bytes (and their normals')
+ * copied, indices renumbered, vert_src and face_src.
+ * Grey (only with images), per input vertex: over the views where the vertex is visible and, with cull = 1,
+ * ((n0 p0 + n1 p1) + n2 p2) < 0 (p = X - c), acc += image[y][x], cnt += 1; grey = cnt ? (2 acc + cnt) / (2 cnt) : fill,
+ * grey_views = cnt.  cull = 1 with images needs normals; without images cull and fill are not used.
+ * Counts, int32: faces_seen (face_views >= 1), faces_back_only (face_views == 0 and face_back_views >= 1), faces_unseen (both 0),
+ * faces_kept, verts_kept.  uint64, over all (vertex, view) pairs: pairs_visible, pairs_occluded (the depth test failed),
+ * pairs_off (not inband, or the pixel outside the image); the three sum to n V.
+ * A key is a function of (face, pixel), a minimum has no order, everything after the one depth comparison is an integer and
+ * every offset comes from a scan, so every output is bit-identical to the NumPy restatement in tests/visib_ref.py whatever the
+ * schedule, the order of the views and their batching. */
+typedef struct sfmx_visib sfmx_visib;  /* the views, their images, the work buffers and the last result; they grow and are kept */
+typedef struct sfmx_visib_params {
+  double z_min;     /* the z-buffer's: a vertex nearer than this is not inband and drops its faces; finite, > 0; no default */
+  double depth_tol; /* a vertex this far behind the z-buffer is still visible; finite, >= 0; no default */
+  int min_views;    /* a face seen from the front by fewer views is removed; >= 0 (default 1) */
+  int cull;         /* grey only: 1 = skip the views a vertex's normal points away from (default), 0 = do not */
+  int fill;         /* grey of a vertex no view contributes to, 0 .. 255 (default 0) */
+} sfmx_visib_params;
+void sfmx_visib_default_params(sfmx_visib_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_visib_check_params(const sfmx_visib_params* p);
+int sfmx_visib_create(sfmx_ctx* ctx, sfmx_visib** out);
+void sfmx_visib_destroy(sfmx_ctx* ctx, sfmx_visib* vb);
+/* drops the views and their images and keeps the memory (and the last result) */
+int sfmx_visib_reset(sfmx_ctx* ctx, sfmx_visib* vb);
+/* appends a view; image u8 [h][w] or NULL, a host pointer or (on_device = 1) a device pointer, copied into the object */
+int sfmx_visib_add_view(sfmx_ctx* ctx, sfmx_visib* vb, const sfmx_fusion_view* view, const uint8_t* image, int on_device);
+/* the same with the left rectified image of st's last sfmx_stereo_disparity call, from where it lies on the device; the view's
+ * size must be the stereo object's */
+int sfmx_visib_add_stereo_view(sfmx_ctx* ctx, sfmx_visib* vb, const sfmx_fusion_view* view, const sfmx_stereo* st);
+int sfmx_visib_view_count(const sfmx_visib* vb);
+/* the views are processed in batches (at most 64 per launch), sized by a memory budget for the key images and the per-view
+ * records; k >= 1 (<= 64) forces k views per batch, 0 restores the automatic size.  The result does not depend on it. */
+int sfmx_visib_set_batch(sfmx_visib* vb, int k);
+/* verts double [n][3], normals double [n][3] or NULL, faces int32 [m][3]; host pointers (copied into the object) or
+ * (on_device = 1) device pointers that are not vb's own result arrays (read in place; they must stay until the call returns);
+ * 0 <= n < 2^24, 0 <= m < 2^30.  A face index outside [0, n) is found on the device without any access through it and gives
+ * SFMX_ERR_INVALID, as do images on some views only and cull = 1 with images and no normals; the object stays usable and a
+ * failed call leaves no result.  V = 0, m = 0, n = 0 and a result with nothing left are not errors. */
+int sfmx_visib_run(sfmx_ctx* ctx, sfmx_visib* vb, const double* verts, const double* normals, int n, const int32_t* faces, int m,
+                   int on_device, const sfmx_visib_params* p);
+/* the last successful run to the host: verts_out / normals_out double [n'][3], faces_out int32 [m'][3], vert_src int32 [n'],
+ * face_src int32 [m'], face_views / face_back_views int32 [m], vert_views int32 [n], grey u8 [n], grey_views int32 [n]; any may
+ * be NULL.  SFMX_ERR_INVALID before a successful run, for normals_out after a run without normals and for grey / grey_views
+ * after a run without images. */
+int sfmx_visib_read(sfmx_ctx* ctx, sfmx_visib* vb, double* verts_out, double* normals_out, int32_t* faces_out, int32_t* vert_src,
+                    int32_t* face_src, int32_t* face_views, int32_t* face_back_views, int32_t* vert_views, uint8_t* grey,
+                    int32_t* grey_views);
+/* input and output vertices and faces (n, m, n', m') of the last successful run; any pointer may be NULL.  SFMX_ERR_INVALID
+ * (and zeros) before a successful run; needs no context. */
+int sfmx_visib_sizes(const sfmx_visib* vb, int* n, int* m, int* n_verts_out, int* n_faces_out);
+/* of the last successful run: counts5 int32 [5] = faces_seen, faces_back_only, faces_unseen, faces_kept, verts_kept and pairs3
+ * uint64 [3] = pairs_visible, pairs_occluded, pairs_off; either may be NULL.  SFMX_ERR_INVALID (and zeros) before one. */
+int sfmx_visib_counts(const sfmx_visib* vb, int32_t* counts5, uint64_t* pairs3);
+/* the culled mesh on the device, the object's own arrays (for sfmx_raster_run, sfmx_simplify_run, sfmx_shade_vertices and
+ * sfmx_sdist_set_target / _query with on_device = 1); any pointer may be NULL.  Returns n', or -1 before a successful run.
+ * Valid until the next run on vb. */
+int sfmx_visib_device_mesh(const sfmx_visib* vb, const double** verts, const int32_t** faces, int* n_verts, int* n_faces);
+/* the culled vertices and their normals (NULL after a run without normals).  Returns n', or -1 before a successful run. */
+int sfmx_visib_device_surface(const sfmx_visib* vb, const double** verts, const double** normals);
+/* device time (us) from the first to the last launch of the last run when timing is on (sfmx_set_timing), else 0 */
+double sfmx_visib_last_us(const sfmx_visib* vb);
+/* the largest number of views the last successful run put into one batch (a property of the schedule, not of the result) */
+int sfmx_visib_last_batch(const sfmx_visib* vb);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

@@ -63,6 +63,9 @@ SYMBOLS = [
     "sfmx_fill_device_mesh", "sfmx_fill_device_surface", "sfmx_fill_last_us",
     "sfmx_raster_default_params", "sfmx_raster_check_params", "sfmx_raster_create", "sfmx_raster_destroy", "sfmx_raster_run",
     "sfmx_raster_read", "sfmx_raster_counts", "sfmx_raster_device_surface", "sfmx_raster_last_us", "sfmx_raster_last_big_faces",
+    "sfmx_visib_default_params", "sfmx_visib_check_params", "sfmx_visib_create", "sfmx_visib_destroy", "sfmx_visib_reset",
+    "sfmx_visib_add_view", "sfmx_visib_add_stereo_view", "sfmx_visib_view_count", "sfmx_visib_set_batch", "sfmx_visib_run", "sfmx_visib_read", "sfmx_visib_sizes",
+    "sfmx_visib_counts", "sfmx_visib_device_mesh", "sfmx_visib_device_surface", "sfmx_visib_last_us", "sfmx_visib_last_batch",
 ]
 
 
@@ -409,6 +412,39 @@ def raster_check_params(z_min=0.0, **kw) -> bool:
     return load_library().sfmx_raster_check_params(byref(raster_params(z_min, **kw))) == SFMX_OK
 
 
+class VisibParams(ctypes.Structure):
+    _fields_ = [("z_min", c_double), ("depth_tol", c_double), ("min_views", c_int), ("cull", c_int), ("fill", c_int)]
+
+
+# z_min and depth_tol have no default (lengths in the mesh's units)
+VISIB_DEFAULTS = dict(min_views=1, cull=1, fill=0)
+VISIB_COUNTS = ("faces_seen", "faces_back_only", "faces_unseen", "faces_kept", "verts_kept", "pairs_visible", "pairs_occluded", "pairs_off")
+VISIB_MAX_BATCH = 64
+
+
+def visib_params(z_min=0.0, depth_tol=-1.0, **kw) -> VisibParams:
+    unknown = set(kw) - set(VISIB_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown visibility parameters {sorted(unknown)}")
+    kw = {**VISIB_DEFAULTS, **kw}
+    for k in VISIB_DEFAULTS:
+        if int(kw[k]) != kw[k]:
+            raise TypeError(f"visibility parameter {k} is an integer")
+    return VisibParams(float(z_min), float(depth_tol), int(kw["min_views"]), int(kw["cull"]), int(kw["fill"]))
+
+
+def visib_default_params() -> dict:
+    """sfmx_visib_default_params as a dict (needs no device)"""
+    p = VisibParams()
+    load_library().sfmx_visib_default_params(byref(p))
+    return {k: getattr(p, k) for k, _ in VisibParams._fields_}
+
+
+def visib_check_params(z_min=0.0, depth_tol=-1.0, **kw) -> bool:
+    """True if sfmx_visib_run would accept the parameters; needs no device"""
+    return load_library().sfmx_visib_check_params(byref(visib_params(z_min, depth_tol, **kw))) == SFMX_OK
+
+
 ALIGN_ITERS_CAP = 64  # SFMX_ALIGN_ITERS_CAP
 ALIGN_CONVERGED, ALIGN_MAX_ITERS, ALIGN_TOO_FEW, ALIGN_DEGENERATE = range(4)
 ALIGN_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")
@@ -497,6 +533,7 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_smooth_last_us.restype = c_double
         _lib.sfmx_fill_last_us.restype = c_double
         _lib.sfmx_raster_last_us.restype = c_double
+        _lib.sfmx_visib_last_us.restype = c_double
     return _lib
 
 
@@ -1426,6 +1463,142 @@ class Raster:
             pass
 
 
+class Visib:
+    """sfmx_visib: which faces and vertices of a mesh a list of cameras really sees, from the exact z-buffer of every camera
+    (DESIGN.md 24): per-face and per-vertex view counts, the mesh without the faces too few cameras see from the front, and a
+    grey value per vertex from the cameras that see it.  The views, their images and the work buffers are kept between runs."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_visib_create(ctx.h_, byref(self.h_)))
+        self.images = 0  # views added with an image
+        self.has_normals = self.has_grey = False  # of the last successful run
+
+    def reset(self):
+        self.ctx._chk(self.ctx.lib.sfmx_visib_reset(self.ctx.h_, self.h_))
+        self.images = 0
+
+    def add_view(self, cam: dict, image=None, w=None, h=None):
+        """cam: dict(R_rw, c_left, f, cx, cy, w, h) (B is not used; w= / h= override the dict's image size).  image: uint8 [h][w]
+        numpy array, an int (device pointer), or None."""
+        w, h = int(cam["w"] if w is None else w), int(cam["h"] if h is None else h)
+        v = fusion_view({**cam, "B": cam.get("B", 0.0)}, w, h)
+        on_dev = isinstance(image, int)
+        if image is None:
+            pi = None
+        elif on_dev:
+            pi = c_void_p(image)
+        else:
+            image = np.ascontiguousarray(image, np.uint8)
+            assert image.shape == (h, w), (image.shape, h, w)
+            pi = image.ctypes.data_as(c_void_p)
+        self.ctx._chk(self.ctx.lib.sfmx_visib_add_view(self.ctx.h_, self.h_, byref(v), pi, c_int(1 if on_dev else 0)))
+        self.images += image is not None
+
+    def view_count(self) -> int:
+        return int(self.ctx.lib.sfmx_visib_view_count(self.h_))
+
+    def set_batch(self, k: int):
+        """k >= 1 forces k views per batch, 0 restores the automatic size; the result does not depend on it"""
+        rc = self.ctx.lib.sfmx_visib_set_batch(self.h_, c_int(int(k)))
+        if rc != SFMX_OK:
+            raise SfmxError(rc, f"sfmx_visib_set_batch: {k} is not in 0 .. {VISIB_MAX_BATCH}")
+
+    def run(self, verts, faces, z_min=0.0, depth_tol=-1.0, normals=None, n=None, m=None, read=True, **params):
+        """verts / normals float64 [n][3] and faces int32 [m][3]: numpy arrays, or ints (device pointers, not this object's own
+        result) with n and m given; normals may be None.  z_min and depth_tol are required; params: VISIB_DEFAULTS keys.  Returns
+        read()'s dict, or counts() with read=False."""
+        p = visib_params(z_min, depth_tol, **params)
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int) or (normals is not None and on_dev != isinstance(normals, int)):
+            raise TypeError("verts, normals and faces: all host arrays or all device pointers")
+        if on_dev:
+            pv, pf, pn = c_void_p(verts), c_void_p(faces), (c_void_p(normals) if normals is not None else None)
+            n, m = int(n), int(m)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            n, m = len(verts), len(faces)
+            normals = None if normals is None else _f64(normals).reshape(-1, 3)
+            assert normals is None or len(normals) == n
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+            pn = normals.ctypes.data_as(c_void_p) if normals is not None else None
+        self.ctx._chk(self.ctx.lib.sfmx_visib_run(self.ctx.h_, self.h_, pv, pn, c_int(n), pf, c_int(m), c_int(1 if on_dev else 0), byref(p)))
+        self.has_normals, self.has_grey = normals is not None, self.images > 0
+        return self.read() if read else self.counts()
+
+    def sizes(self):
+        """(n, m, n', m') of the last successful run; raises before one"""
+        s = [c_int(0) for _ in range(4)]
+        rc = self.ctx.lib.sfmx_visib_sizes(self.h_, *[byref(x) for x in s])
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_visib_sizes: no successful run")
+        return tuple(x.value for x in s)
+
+    def counts(self) -> dict:
+        """dict of VISIB_COUNTS of the last successful run; raises before one"""
+        c, pr = (c_int32 * 5)(), (c_uint64 * 3)()
+        rc = self.ctx.lib.sfmx_visib_counts(self.h_, c, pr)
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_visib_counts: no successful run")
+        return dict(zip(VISIB_COUNTS, [int(x) for x in c] + [int(x) for x in pr]))
+
+    def read(self, normals=None, grey=None) -> dict:
+        """the last run: dict(verts f64 [n'][3], faces i32 [m'][3], vert_src i32 [n'], face_src i32 [m'], face_views /
+        face_back_views i32 [m], vert_views i32 [n], the VISIB_COUNTS), plus normals f64 [n'][3] and grey u8 [n] / grey_views i32
+        [n].  normals / grey: True asks for them (the library refuses what the run did not have), None takes what there is."""
+        n, m, nv, nf = self.sizes()
+        lib = self.ctx.lib
+        normals = self.has_normals if normals is None else normals
+        grey = self.has_grey if grey is None else grey
+        z = lambda k, *s, t=np.float64: np.zeros((max(k, 1),) + s, t)
+        verts, nrm, faces = z(nv, 3), z(nv, 3), z(nf, 3, t=np.int32)
+        vsrc, fsrc = z(nv, t=np.int32), z(nf, t=np.int32)
+        fviews, fback, vviews = z(m, t=np.int32), z(m, t=np.int32), z(n, t=np.int32)
+        g, gv = z(n, t=np.uint8), z(n, t=np.int32)
+        self.ctx._chk(lib.sfmx_visib_read(self.ctx.h_, self.h_, _p(verts, c_double), _p(nrm, c_double) if normals else None,
+                                          _p(faces, c_int32), _p(vsrc, c_int32), _p(fsrc, c_int32), _p(fviews, c_int32), _p(fback, c_int32),
+                                          _p(vviews, c_int32), _p(g, c_uint8) if grey else None, _p(gv, c_int32) if grey else None))
+        out = dict(verts=verts[:nv].copy(), faces=faces[:nf].copy(), vert_src=vsrc[:nv].copy(), face_src=fsrc[:nf].copy(),
+                   face_views=fviews[:m].copy(), face_back_views=fback[:m].copy(), vert_views=vviews[:n].copy(), **self.counts())
+        if normals:
+            out["normals"] = nrm[:nv].copy()
+        if grey:
+            out["grey"], out["grey_views"] = g[:n].copy(), gv[:n].copy()
+        return out
+
+    def device_mesh(self):
+        """(n', device pointer of the kept vertices, of the kept faces, m'); n' = -1 before a successful run"""
+        v, f, nv, m = c_void_p(), c_void_p(), c_int(0), c_int(0)
+        n = int(self.ctx.lib.sfmx_visib_device_mesh(self.h_, byref(v), byref(f), byref(nv), byref(m)))
+        return n, v.value, f.value, int(m.value)
+
+    def device_surface(self):
+        """(n', device pointer of the kept vertices, of their normals or None); n' = -1 before a successful run"""
+        v, nr = c_void_p(), c_void_p()
+        n = int(self.ctx.lib.sfmx_visib_device_surface(self.h_, byref(v), byref(nr)))
+        return n, v.value, nr.value
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_visib_last_us(self.h_))
+
+    def last_batch(self) -> int:
+        """the largest number of views the last run put into one batch"""
+        return int(self.ctx.lib.sfmx_visib_last_batch(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_visib_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Align:
     """sfmx_align: registration of a view to a TSDF volume by direct Gauss-Newton alignment.  The device work
     buffers grow on demand and are kept between calls."""
@@ -1872,6 +2045,9 @@ class Context:
 
     def raster(self) -> "Raster":
         return Raster(self)
+
+    def visib(self) -> "Visib":
+        return Visib(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

@@ -103,6 +103,16 @@
 #pragma weak sfmx_raster_run
 #pragma weak sfmx_raster_read
 #pragma weak sfmx_raster_counts
+#pragma weak sfmx_visib_check_params
+#pragma weak sfmx_visib_create
+#pragma weak sfmx_visib_destroy
+#pragma weak sfmx_visib_add_view
+#pragma weak sfmx_visib_add_stereo_view
+#pragma weak sfmx_visib_run
+#pragma weak sfmx_visib_read
+#pragma weak sfmx_visib_sizes
+#pragma weak sfmx_visib_counts
+#pragma weak sfmx_visib_device_mesh
 
 namespace {
 
@@ -120,7 +130,9 @@ struct Guard {
   sfmx_smooth* ta = nullptr;
   sfmx_fill* fl = nullptr;
   sfmx_raster* rs = nullptr;
+  sfmx_visib* vb = nullptr;
   ~Guard() {
+    if (vb) sfmx_visib_destroy(ctx, vb);
     if (rs) sfmx_raster_destroy(ctx, rs);
     if (fl) sfmx_fill_destroy(ctx, fl);
     if (ta) sfmx_smooth_destroy(ctx, ta);
@@ -392,10 +404,44 @@ int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
                              sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_vs(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts, gt,
+                                  ev, render, align, simplify, simplify_counts, smooth, smooth_counts, fill, fill_counts, raster, nullptr, res,
+                                  ply_path, warn, warn_cap);
+}
+
+void sfmx_host_visib_free(sfmx_visib_request* visib) {
+  if (!visib) return;
+  std::free(visib->face_views);
+  std::free(visib->face_back_views);
+  std::free(visib->vert_views);
+  visib->face_views = visib->face_back_views = visib->vert_views = nullptr;
+}
+
+int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_visib_request* visib, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
   if (warn && warn_cap > 0) warn[0] = 0;
+  sfmx_visib_params vp{};
+  if (visib) {
+    for (int32_t& c : visib->counts) c = 0;
+    for (uint64_t& c : visib->pairs) c = 0;
+    visib->n_in = visib->m_in = 0;
+    visib->face_views = visib->face_back_views = visib->vert_views = nullptr;
+    if (!&sfmx_visib_check_params || !&sfmx_visib_create || !&sfmx_visib_destroy || !&sfmx_visib_add_view || !&sfmx_visib_add_stereo_view ||
+        !&sfmx_visib_run || !&sfmx_visib_read || !&sfmx_visib_sizes || !&sfmx_visib_counts || !&sfmx_visib_device_mesh)
+      return SFMX_ERR_UNSUPPORTED;
+    vp = visib->params;
+    if (vp.depth_tol == 0.0) vp.depth_tol = fp->voxel;
+    if (sfmx_visib_check_params(&vp) != SFMX_OK || (visib->colour != 0 && visib->colour != 1) || (visib->colour && !app)) return SFMX_ERR_INVALID;
+  }
   if (!&sfmx_fusion_create || !&sfmx_stereo_disparity) return SFMX_ERR_UNSUPPORTED;
   if (app && (!&sfmx_shade_create || !&sfmx_fusion_extract_normals)) return SFMX_ERR_UNSUPPORTED;
   if (cs && (!&sfmx_consist_create || !&sfmx_fusion_add_consist_view)) return SFMX_ERR_UNSUPPORTED;
@@ -512,6 +558,10 @@ int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on
     rc = sfmx_shade_create(ctx, &g.sh);
     if (rc != SFMX_OK) return rc;
   }
+  if (visib) {
+    rc = sfmx_visib_create(ctx, &g.vb);
+    if (rc != SFMX_OK) return rc;
+  }
   std::vector<int16_t> d16((size_t)w * h);  // sfmx_stereo_disparity always returns the map to the host
   for (int q = 0; q < m; q++) {
     const int a = pairs[2 * q], b = pairs[2 * q + 1];
@@ -564,6 +614,10 @@ int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on
     if (cs) listed.push_back(q);
     if (app) {
       rc = sfmx_shade_add_stereo_view(ctx, g.sh, &v, g.st);
+      if (rc != SFMX_OK) return rc;
+    }
+    if (visib) {  // the view as it entered the volume; its left rectified image only when the stage colours
+      rc = visib->colour ? sfmx_visib_add_stereo_view(ctx, g.vb, &v, g.st) : sfmx_visib_add_view(ctx, g.vb, &v, nullptr, 0);
       if (rc != SFMX_OK) return rc;
     }
     res->n_views++;
@@ -761,6 +815,68 @@ int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on
     res->n_verts = nv;
     res->n_faces = nf;
   }
+  // visibility runs on the final mesh, fed from the result arrays (the same bytes as the device copy the last stage left: a run
+  // takes its arrays from one side, and a smoothed mesh keeps its normals in another object than its vertices).  The culled mesh
+  // replaces the result arrays in place and lies inside the visib object for the evaluation below.
+  bool culled = false;
+  if (visib && nf > 0) {
+    const int nv0 = nv, nf0 = nf;
+    visib->n_in = nv0;
+    visib->m_in = nf0;
+    rc = sfmx_visib_run(ctx, g.vb, res->verts, app ? res->normals : nullptr, nv0, res->faces, nf0, 0, &vp);
+    if (rc == SFMX_OK) rc = sfmx_visib_sizes(g.vb, nullptr, nullptr, &nv, &nf);
+    if (rc == SFMX_OK) rc = sfmx_visib_counts(g.vb, visib->counts, visib->pairs);
+    std::vector<double> cv, cn;
+    std::vector<int32_t> cf, vsrc, vc;
+    std::vector<uint8_t> vg;
+    if (rc == SFMX_OK) {
+      visib->face_views = static_cast<int32_t*>(std::malloc((size_t)nf0 * sizeof(int32_t)));
+      visib->face_back_views = static_cast<int32_t*>(std::malloc((size_t)nf0 * sizeof(int32_t)));
+      visib->vert_views = static_cast<int32_t*>(std::malloc((size_t)nv0 * sizeof(int32_t)));
+      if (!visib->face_views || !visib->face_back_views || !visib->vert_views) rc = SFMX_ERR_INVALID;
+    }
+    if (rc == SFMX_OK) {
+      cv.resize((size_t)nv * 3);
+      cn.resize(app ? (size_t)nv * 3 : 0);
+      cf.resize((size_t)nf * 3);
+      vsrc.resize((size_t)nv);
+      if (visib->colour) {
+        vg.resize((size_t)nv0);
+        vc.resize((size_t)nv0);
+      }
+      rc = sfmx_visib_read(ctx, g.vb, cv.data(), app ? cn.data() : nullptr, cf.data(), vsrc.data(), nullptr, visib->face_views,
+                           visib->face_back_views, visib->vert_views, visib->colour ? vg.data() : nullptr,
+                           visib->colour ? vc.data() : nullptr);
+    }
+    if (rc != SFMX_OK) {
+      const int keep = res->n_views;
+      sfmx_host_fusion_free_ex(res);
+      res->n_views = keep;
+      sfmx_host_visib_free(visib);
+      return rc;
+    }
+    if (nf == 0) {  // nothing left: as a volume without a surface
+      const int keep = res->n_views;
+      sfmx_host_fusion_free_ex(res);
+      res->n_views = keep;
+      nv = 0;
+    } else {
+      std::memcpy(res->verts, cv.data(), (size_t)nv * 3 * sizeof(double));
+      std::memcpy(res->faces, cf.data(), (size_t)nf * 3 * sizeof(int32_t));
+      if (app) {
+        std::memcpy(res->normals, cn.data(), (size_t)nv * 3 * sizeof(double));
+        // vert_src ascends and vert_src[i] >= i: the gather can run in place
+        for (int i = 0; i < nv; i++) {
+          const size_t s = (size_t)vsrc[(size_t)i];
+          res->grey[i] = visib->colour ? vg[s] : res->grey[s];
+          res->views[i] = visib->colour ? vc[s] : res->views[s];
+        }
+      }
+      res->n_verts = nv;
+      res->n_faces = nf;
+    }
+    culled = true;
+  }
   if (gt) {
     // the final mesh is still on the device (inside the simplify or the clean object, or inside the volume after the last
     // extraction): it is the query set of the accuracy and the target of the completeness, with no host round trip
@@ -772,10 +888,13 @@ int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on
     std::vector<uint8_t> used;
     std::vector<double> d2((size_t)(nf > 0 ? nv : 0));
     rc = sfmx_sdist_create(ctx, &g.sd);
-    if (rc == SFMX_OK && simplified && nf > 0 && (sfmx_simplify_device_mesh(g.sm, &mv, &mf, &mnf) != nv || mnf != nf))
+    if (rc == SFMX_OK && !culled && simplified && nf > 0 && (sfmx_simplify_device_mesh(g.sm, &mv, &mf, &mnf) != nv || mnf != nf))
       rc = SFMX_ERR_INVALID;
-    const bool own = simplified || smoothed || filled;  // the final mesh is handed over as device pointers
-    if (!simplified && smoothed) {
+    const bool own = culled || simplified || smoothed || filled;  // the final mesh is handed over as device pointers
+    if (culled) {  // the culled mesh lies inside the visib object
+      int cnv = 0;
+      if (rc == SFMX_OK && nf > 0 && (sfmx_visib_device_mesh(g.vb, &mv, &mf, &cnv, &mnf) != nv || mnf != nf)) rc = SFMX_ERR_INVALID;
+    } else if (!simplified && smoothed) {
       mv = sdv;
       mf = sdf;
     } else if (!simplified && filled) {
@@ -806,6 +925,7 @@ int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on
       sfmx_host_fusion_free_ex(res);
       res->n_views = keep;
       *ev = sfmx_surface_eval_result{};
+      sfmx_host_visib_free(visib);
       return rc;
     }
     eval_side(d2, nullptr, gt->params, &ev->n_gt, &ev->comp_within, nullptr, nullptr, nullptr);
@@ -825,6 +945,7 @@ int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on
       sfmx_host_fusion_free_ex(res);
       res->n_views = keep;
       if (gt) *ev = sfmx_surface_eval_result{};
+      sfmx_host_visib_free(visib);
       return rc;
     }
   }
@@ -849,6 +970,7 @@ int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on
       sfmx_host_fusion_free_ex(res);
       res->n_views = keep;
       if (gt) *ev = sfmx_surface_eval_result{};
+      sfmx_host_visib_free(visib);
       return rc;
     }
   }

@@ -229,4 +229,32 @@ int sfmx_host_fusion_mesh_rs(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
                              sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_rs with the faces no camera sees from the front removed from the final mesh.  visib =
+// NULL: exactly sfmx_host_fusion_mesh_rs.  Otherwise the views are the integrated pairs' left rectified cameras at the image
+// size (the refined ones with align), the stage runs on the final mesh after simplifying, and the shading's result arrays, the
+// evaluation, the z-buffer renders and the PLY all take the culled mesh; the grey and views of a kept vertex are those it had.
+// params.depth_tol == 0 stands for the voxel.  colour = 1 (needs app) replaces grey and views by this stage's grey and
+// grey_views, from the pairs' left rectified images.  The request's outputs are filled: the counts, the sizes before culling and
+// face_views / face_back_views [m_in], vert_views [n_in] (malloc'ed here, NULL for an empty surface; release them with
+// sfmx_host_visib_free).  A surface with nothing left is no error: the result then has no arrays, as a volume without a surface.
+struct sfmx_visib_request {
+  sfmx_visib_params params;
+  int colour;
+  int32_t counts[5];   // faces_seen, faces_back_only, faces_unseen, faces_kept, verts_kept
+  uint64_t pairs[3];   // pairs_visible, pairs_occluded, pairs_off
+  int32_t n_in, m_in;  // vertices and faces of the mesh that entered the stage
+  int32_t* face_views;
+  int32_t* face_back_views;
+  int32_t* vert_views;
+};
+void sfmx_host_visib_free(sfmx_visib_request* visib);
+int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_visib_request* visib, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
 }

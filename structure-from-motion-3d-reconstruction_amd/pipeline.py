@@ -226,6 +226,14 @@ class RasterRequest(ctypes.Structure):
     _fields_ = [("cameras", POINTER(capi.FusionView)), ("n_cameras", c_int), ("params", capi.RasterParams), ("out", POINTER(RasterOut))]
 
 
+VISIBILITY_KEYS = ("z_min", "depth_tol", "min_views", "colour", "cull", "fill")
+
+
+class VisibRequest(ctypes.Structure):
+    _fields_ = [("params", capi.VisibParams), ("colour", c_int), ("counts", c_int * 5), ("pairs", ctypes.c_uint64 * 3), ("n_in", c_int),
+                ("m_in", c_int), ("face_views", POINTER(c_int)), ("face_back_views", POINTER(c_int)), ("vert_views", POINTER(c_int))]
+
+
 ALIGN_KEYS = ("seed", "max_iters", "stride", "min_pixels", "damping", "eps_rot", "eps_trans", "min_weight")
 
 
@@ -286,7 +294,7 @@ def _split_fusion_params(params: dict):
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
          consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, fill=False, raster=None,
-         **params) -> dict:
+         visibility=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -337,7 +345,13 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     mesh, the one in the arrays and the PLY, is rendered from each camera at w x h by the exact z-buffer (z_min is
     required): the dict gains rasters = [dict(depth, face, points, normals, shaded, the capi.RASTER_COUNTS, fragments), ...]; with
     appearance the vertex normals and grey are interpolated and each also carries grey.  pgm_prefix writes
-    <prefix>_<i>_mesh_shaded.pgm (and _mesh_grey.pgm with appearance).  Everything else is what it is without raster."""
+    <prefix>_<i>_mesh_shaded.pgm (and _mesh_grey.pgm with appearance).  Everything else is what it is without raster.
+    visibility: dict(z_min=, depth_tol=, min_views=1, colour=False, cull=1, fill=0) -- the faces of the final mesh (after simplify)
+    that fewer than min_views of the integrated pairs' left rectified cameras (the refined ones with align) see from the front are
+    removed on the device (z_min is required, depth_tol defaults to the voxel) before the mesh is shaded, evaluated,
+    rendered by raster and written.  The dict gains visibility = dict(face_views, face_back_views, vert_views (per element of the
+    mesh that entered the stage), the capi.VISIB_COUNTS, verts_removed, faces_removed).  colour=True (needs appearance) replaces
+    grey / vertex_views and the PLY colour by this stage's, from the pairs' left rectified images (cull and fill are its)."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -470,6 +484,18 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                       a["grey"].ctypes.data_as(POINTER(c_ubyte)) if ap is not None else None) for a in zarr])
         zq = RasterRequest(zviews, len(zcams), capi.raster_params(zkw["z_min"], cull=zkw.get("cull", 0), background=zkw.get("background", 0)),
                            zouts)
+    vq = None
+    if visibility:
+        vkw = {} if visibility is True else dict(visibility)
+        unknown = set(vkw) - set(VISIBILITY_KEYS)
+        if unknown:
+            raise TypeError(f"unknown visibility parameters {sorted(unknown)}")
+        if "z_min" not in vkw:
+            raise TypeError("visibility needs z_min")
+        vcolour = bool(vkw.pop("colour", False))
+        if vcolour and ap is None:
+            raise TypeError("visibility colour=True needs appearance")
+        vq = VisibRequest(capi.visib_params(vkw.pop("z_min"), vkw.pop("depth_tol", 0.0), **vkw), int(vcolour))  # 0 = the voxel
     aq = None
     if align:
         gkw = {} if align is True else dict(align)
@@ -479,12 +505,26 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         seed = int(gkw.pop("seed", 1))
         aouts = (capi.AlignResult * max(len(pr), 1))()
         aq = AlignRequest(seed, capi.align_params(disp_min=fp.disp_min, **gkw), aouts)
-    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None or hp is not None or zq is not None:
+    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None or hp is not None or zq is not None or vq is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if zq is not None:
+        if vq is not None:
+            rc = lib.sfmx_host_fusion_mesh_vs(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None,
+                                              byref(rq) if rq is not None else None, byref(aq) if aq is not None else None,
+                                              byref(mp) if mp is not None else None,
+                                              mcounts.ctypes.data_as(POINTER(c_int)) if mp is not None else None,
+                                              byref(tp) if tp is not None else None,
+                                              tcounts.ctypes.data_as(POINTER(c_int)) if tp is not None else None,
+                                              byref(hp) if hp is not None else None,
+                                              hcounts.ctypes.data_as(POINTER(c_int)) if hp is not None else None,
+                                              byref(zq) if zq is not None else None, byref(vq), *tail)
+        elif zq is not None:
             rc = lib.sfmx_host_fusion_mesh_rs(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -556,6 +596,13 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         if rc != capi.SFMX_OK:
             raise capi.SfmxError(rc, (ctx.lib.sfmx_last_error(ctx.h_) or b"").decode() or "fuse")
         try:
+            if vq is not None:
+                vn, vm = int(vq.n_in), int(vq.m_in)
+                vis = dict(face_views=np.ctypeslib.as_array(vq.face_views, (vm,)).astype(np.int32) if vm else np.zeros(0, np.int32),
+                           face_back_views=np.ctypeslib.as_array(vq.face_back_views, (vm,)).astype(np.int32) if vm else np.zeros(0, np.int32),
+                           vert_views=np.ctypeslib.as_array(vq.vert_views, (vn,)).astype(np.int32) if vn else np.zeros(0, np.int32),
+                           **dict(zip(capi.VISIB_COUNTS, [int(c) for c in vq.counts] + [int(c) for c in vq.pairs])))
+                vis.update(verts_removed=vn - vis["verts_kept"], faces_removed=vm - vis["faces_kept"])
             nv, nf = (rex.n_verts, rex.n_faces) if rex.n_faces else (0, 0)
             verts = np.ctypeslib.as_array(rex.verts, (nv, 3)).copy() if nf else np.zeros((0, 3))
             faces = np.ctypeslib.as_array(rex.faces, (nf, 3)).astype(np.int32) if nf else np.zeros((0, 3), np.int32)
@@ -566,6 +613,10 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                 out["vertex_views"] = np.ctypeslib.as_array(rex.views, (nv,)).astype(np.int32) if nf else np.zeros(0, np.int32)
         finally:
             lib.sfmx_host_fusion_free_ex(byref(rex))
+            if vq is not None:
+                lib.sfmx_host_visib_free(byref(vq))
+        if vq is not None:
+            out["visibility"] = vis
         if cp is not None:
             done = counts[:len(pr)][counts[:len(pr), 0] >= 0]
             out["consistency"] = dict(valid=[int(v) for v in done[:, 0]], kept=[int(v) for v in done[:, 1]])
@@ -659,7 +710,8 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     a ground-truth mesh; 'render' (a dict, as fuse) ray casts the volume from further cameras; 'align' (True or a dict, as fuse) registers each later
     pair's view to the volume before it enters it; 'simplify' (True or a dict, as fuse) simplifies the final surface by exact vertex
     clustering; 'smooth' (True or a dict, as fuse) smooths it with the exact Taubin filter first; 'fill' (True or a dict, as fuse) fills its small
-    holes before that; 'raster' (a dict, as fuse) renders the final mesh from further cameras.  The run itself, its log and every other output are unchanged.
+    holes before that; 'raster' (a dict, as fuse) renders the final mesh from further cameras; 'visibility' (a dict, as fuse) first removes
+    the faces no pair's camera sees from the front.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -730,9 +782,10 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         smooth = fz.pop("smooth", False)
         fill = fz.pop("fill", False)
         raster = fz.pop("raster", None)
+        visibility = fz.pop("visibility", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
                                  appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align,
-                                 simplify=simplify, smooth=smooth, fill=fill, raster=raster, **fz)
+                                 simplify=simplify, smooth=smooth, fill=fill, raster=raster, visibility=visibility, **fz)
     return out
 
 

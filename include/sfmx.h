@@ -934,6 +934,80 @@ double sfmx_visib_last_us(const sfmx_visib* vb);
 /* the largest number of views the last successful run put into one batch (a property of the schedule, not of the result) */
 int sfmx_visib_last_batch(const sfmx_visib* vb);
 
+/* ---- a texture atlas from the cameras that see the mesh: best view per face, one patch per face ------------- */
+/* The object holds an ordered list of V >= 1 views, each a sfmx_fusion_view under the z-buffer's camera rules above (B ignored,
+ * sizes may differ) with an image u8 [h][w]; a run needs an image on every view.
+ * Seen: face f is seen by view k exactly as sfmx_visib defines it (its three vertices visible in k, A < 0).
+ * Best view: face_view[f] is the seen view with the largest -A (int64), a tie goes to the smallest view index, face_area[f] is
+ * that -A; a face no view sees has face_view = -1 and face_area = 0.  view_faces[k] counts the faces of view k.
+ * Layout, S = patch, L = S - 2: the textured faces in ascending index get ranks r = 0, 1, ...; rank r uses cell r >> 1, half
+ * r & 1.  cells = ceil(n_tex / 2) + (n_un > 0 ? 1 : 0); the extra last cell is the fill cell.  A cell is S + 1 texels wide and S
+ * high.  C = cells_per_row, or with 0 the smallest C with C C >= cells, at least 1, at most floor(16384 / (S + 1)).  The atlas is
+ * W = C (S + 1) wide and H = ceil(cells / C) S high (W = H = 0 with cells = 0); cell c has its top-left texel at
+ * ((c % C) (S + 1), (c / C) S).  W > 16384 or W H > 2^28 is SFMX_ERR_INVALID, decided before the atlas is allocated.
+ * Ownership: half 0 owns the local texels (i, j), i, j >= 0, i + j <= S - 1; half 1 owns (S - i, S - 1 - j) for the same (i, j).
+ * A texel of the fill cell, of a half without a face and of a cell past the last one is `fill`.
+ * Corners, in half-texels relative to the cell: half 0 has a at (1, 1), b at (2 S - 3, 1), c at (1, 2 S - 3); half 1 the half
+ * turn (2 (S + 1) - x, 2 S - y).  uv_half int32 [m][3][2] holds them plus twice the cell's origin; an untextured face has all
+ * three on the centre of the fill cell, (2 x0 + S + 1, 2 y0 + S).  u = hx / (2 W), v = 1 - hy / (2 H).
+ * Texel (i, j) of face (a, b, c) with view k: i' = min(i, L), j' = min(j, L - i') (the texels with i + j = S - 1 repeat the
+ * hypotenuse); X_r = (((double)(L - i' - j') Xa_r + (double)i' Xb_r) + (double)j' Xc_r) / (double)L; p = X - c,
+ * q_r = (R[r][0] p0 + R[r][1] p1) + R[r][2] p2, u = (f q0) / q2 + cx, v = (f q1) / q2 + cy; `fill` unless q2 > 0 and u, v finite;
+ * uc = min(max(u, -1), w), x0 = floor(uc), ax = uc - x0, xi0 = clamp((int)x0, 0, w - 1), xi1 = clamp((int)x0 + 1, 0, w - 1),
+ * likewise v and h; top = (1 - ax) I[yi0][xi0] + ax I[yi0][xi1], bot likewise on yi1, g = (1 - ay) top + ay bot;
+ * texel = (u8)min(255, floor(g + 0.5)).  A pixel is its centre.  Nothing is contracted.
+ * Counts, int32: faces_textured, faces_untextured, cells, W, H, cells_per_row.
+ * Every output is bit-identical to the NumPy restatement in tests/texture_ref.py whatever the schedule and the batching. */
+typedef struct sfmx_texture sfmx_texture;  /* the views, their images, the work buffers and the last result; they grow and are kept */
+typedef struct sfmx_texture_params {
+  double z_min;      /* the z-buffer's; finite, > 0; no default */
+  double depth_tol;  /* a vertex this far behind the z-buffer is still visible; finite, >= 0; no default */
+  int patch;         /* S: a face's patch is S texels along each leg, its cell S + 1 by S; 3 .. 64 (default 8) */
+  int cells_per_row; /* C >= 1, or 0 for the automatic value (default) */
+  int fill;          /* the texel no face owns, 0 .. 255 (default 0) */
+} sfmx_texture_params;
+void sfmx_texture_default_params(sfmx_texture_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_texture_check_params(const sfmx_texture_params* p);
+int sfmx_texture_create(sfmx_ctx* ctx, sfmx_texture** out);
+void sfmx_texture_destroy(sfmx_ctx* ctx, sfmx_texture* tx);
+/* drops the views and their images and keeps the memory (and the last result) */
+int sfmx_texture_reset(sfmx_ctx* ctx, sfmx_texture* tx);
+/* appends a view; image u8 [h][w], a host pointer or (on_device = 1) a device pointer, copied into the object.  NULL is
+ * accepted here and refused by the run. */
+int sfmx_texture_add_view(sfmx_ctx* ctx, sfmx_texture* tx, const sfmx_fusion_view* view, const uint8_t* image, int on_device);
+/* the same with the left rectified image of st's last sfmx_stereo_disparity call, from where it lies on the device */
+int sfmx_texture_add_stereo_view(sfmx_ctx* ctx, sfmx_texture* tx, const sfmx_fusion_view* view, const sfmx_stereo* st);
+int sfmx_texture_view_count(const sfmx_texture* tx);
+/* as sfmx_visib_set_batch: k >= 1 (<= 64) forces k views per batch, 0 restores the automatic size; the result does not depend
+ * on it */
+int sfmx_texture_set_batch(sfmx_texture* tx, int k);
+/* verts double [n][3], faces int32 [m][3]; host pointers (copied into the object) or (on_device = 1) device pointers (read in
+ * place; they must stay until the call returns); 0 <= n < 2^24, 0 <= m < 2^30.  SFMX_ERR_INVALID for a face index outside
+ * [0, n) (found on the device without any access through it), no views, a view without an image, parameters outside their
+ * range and an atlas that is too wide or too large; the object stays usable and a failed call leaves no result.  m = 0 (an
+ * atlas of 0 x 0) and a mesh no view sees (the fill cell alone) are not errors. */
+int sfmx_texture_run(sfmx_ctx* ctx, sfmx_texture* tx, const double* verts, int n, const int32_t* faces, int m, int on_device,
+                     const sfmx_texture_params* p);
+/* the last successful run to the host: atlas u8 [H][W], face_view int32 [m], face_area int64 [m], uv_half int32 [m][3][2],
+ * view_faces int32 [V]; any may be NULL.  SFMX_ERR_INVALID before a successful run. */
+int sfmx_texture_read(sfmx_ctx* ctx, sfmx_texture* tx, uint8_t* atlas, int32_t* face_view, int64_t* face_area, int32_t* uv_half,
+                      int32_t* view_faces);
+/* n, m, V, W and H of the last successful run; any pointer may be NULL.  SFMX_ERR_INVALID (and zeros) before one. */
+int sfmx_texture_sizes(const sfmx_texture* tx, int* n, int* m, int* n_views, int* W, int* H);
+/* counts6 int32 [6] = faces_textured, faces_untextured, cells, W, H, cells_per_row.  SFMX_ERR_INVALID (and zeros) before a
+ * successful run. */
+int sfmx_texture_counts(const sfmx_texture* tx, int32_t* counts6);
+/* the atlas on the device, the object's own array; any pointer may be NULL.  Returns W H, or -1 before a successful run.  Valid
+ * until the next run on tx. */
+int sfmx_texture_device_atlas(const sfmx_texture* tx, const uint8_t** atlas, int* W, int* H);
+/* device time (us) from the first to the last launch of the last run, and of the bake kernel alone, when timing is on
+ * (sfmx_set_timing), else 0 */
+double sfmx_texture_last_us(const sfmx_texture* tx);
+double sfmx_texture_last_bake_us(const sfmx_texture* tx);
+/* the largest number of views the last successful run put into one batch (a property of the schedule, not of the result) */
+int sfmx_texture_last_batch(const sfmx_texture* tx);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

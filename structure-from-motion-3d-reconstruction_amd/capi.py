@@ -66,6 +66,10 @@ SYMBOLS = [
     "sfmx_visib_default_params", "sfmx_visib_check_params", "sfmx_visib_create", "sfmx_visib_destroy", "sfmx_visib_reset",
     "sfmx_visib_add_view", "sfmx_visib_add_stereo_view", "sfmx_visib_view_count", "sfmx_visib_set_batch", "sfmx_visib_run", "sfmx_visib_read", "sfmx_visib_sizes",
     "sfmx_visib_counts", "sfmx_visib_device_mesh", "sfmx_visib_device_surface", "sfmx_visib_last_us", "sfmx_visib_last_batch",
+    "sfmx_texture_default_params", "sfmx_texture_check_params", "sfmx_texture_create", "sfmx_texture_destroy", "sfmx_texture_reset",
+    "sfmx_texture_add_view", "sfmx_texture_add_stereo_view", "sfmx_texture_view_count", "sfmx_texture_set_batch", "sfmx_texture_run",
+    "sfmx_texture_read", "sfmx_texture_sizes", "sfmx_texture_counts", "sfmx_texture_device_atlas", "sfmx_texture_last_us",
+    "sfmx_texture_last_bake_us", "sfmx_texture_last_batch",
 ]
 
 
@@ -445,6 +449,48 @@ def visib_check_params(z_min=0.0, depth_tol=-1.0, **kw) -> bool:
     return load_library().sfmx_visib_check_params(byref(visib_params(z_min, depth_tol, **kw))) == SFMX_OK
 
 
+class TextureParams(ctypes.Structure):
+    _fields_ = [("z_min", c_double), ("depth_tol", c_double), ("patch", c_int), ("cells_per_row", c_int), ("fill", c_int)]
+
+
+# z_min and depth_tol have no default (lengths in the mesh's units)
+TEXTURE_DEFAULTS = dict(patch=8, cells_per_row=0, fill=0)
+TEXTURE_COUNTS = ("faces_textured", "faces_untextured", "cells", "W", "H", "cells_per_row")
+
+
+def texture_params(z_min=0.0, depth_tol=-1.0, **kw) -> TextureParams:
+    unknown = set(kw) - set(TEXTURE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown texture parameters {sorted(unknown)}")
+    kw = {**TEXTURE_DEFAULTS, **kw}
+    for k in TEXTURE_DEFAULTS:
+        if int(kw[k]) != kw[k]:
+            raise TypeError(f"texture parameter {k} is an integer")
+    return TextureParams(float(z_min), float(depth_tol), int(kw["patch"]), int(kw["cells_per_row"]), int(kw["fill"]))
+
+
+def texture_default_params() -> dict:
+    """sfmx_texture_default_params as a dict (needs no device)"""
+    p = TextureParams()
+    load_library().sfmx_texture_default_params(byref(p))
+    return {k: getattr(p, k) for k, _ in TextureParams._fields_}
+
+
+def texture_check_params(z_min=0.0, depth_tol=-1.0, **kw) -> bool:
+    """True if sfmx_texture_run would accept the parameters; needs no device"""
+    return load_library().sfmx_texture_check_params(byref(texture_params(z_min, depth_tol, **kw))) == SFMX_OK
+
+
+def texture_uv(uv_half, W, H):
+    """float64 [m][3][2] from the corners in half-texels: u = hx / (2 W), v = 1 - hy / (2 H) (zeros for an empty atlas)"""
+    uvh = np.asarray(uv_half, np.float64)
+    out = np.zeros(uvh.shape)
+    if W and H:
+        out[..., 0] = uvh[..., 0] / (2.0 * W)
+        out[..., 1] = 1.0 - uvh[..., 1] / (2.0 * H)
+    return out
+
+
 ALIGN_ITERS_CAP = 64  # SFMX_ALIGN_ITERS_CAP
 ALIGN_CONVERGED, ALIGN_MAX_ITERS, ALIGN_TOO_FEW, ALIGN_DEGENERATE = range(4)
 ALIGN_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")
@@ -534,6 +580,8 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_fill_last_us.restype = c_double
         _lib.sfmx_raster_last_us.restype = c_double
         _lib.sfmx_visib_last_us.restype = c_double
+        _lib.sfmx_texture_last_us.restype = c_double
+        _lib.sfmx_texture_last_bake_us.restype = c_double
     return _lib
 
 
@@ -1599,6 +1647,123 @@ class Visib:
             pass
 
 
+class Texture:
+    """sfmx_texture: a texture atlas for a mesh from the cameras that see it: per face the view that sees it from
+    the front with the largest image area, two faces to a cell of (patch + 1) x patch texels, every texel sampled bilinearly
+    from that view's image.  The views, their images and the work buffers are kept between runs."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_texture_create(ctx.h_, byref(self.h_)))
+
+    def reset(self):
+        self.ctx._chk(self.ctx.lib.sfmx_texture_reset(self.ctx.h_, self.h_))
+
+    def add_view(self, cam: dict, image=None, w=None, h=None):
+        """cam: dict(R_rw, c_left, f, cx, cy, w, h) (B is not used; w= / h= override the dict's image size).  image: uint8 [h][w]
+        numpy array or an int (device pointer); None is accepted here and refused by run()."""
+        w, h = int(cam["w"] if w is None else w), int(cam["h"] if h is None else h)
+        v = fusion_view({**cam, "B": cam.get("B", 0.0)}, w, h)
+        on_dev = isinstance(image, int)
+        if image is None:
+            pi = None
+        elif on_dev:
+            pi = c_void_p(image)
+        else:
+            image = np.ascontiguousarray(image, np.uint8)
+            assert image.shape == (h, w), (image.shape, h, w)
+            pi = image.ctypes.data_as(c_void_p)
+        self.ctx._chk(self.ctx.lib.sfmx_texture_add_view(self.ctx.h_, self.h_, byref(v), pi, c_int(1 if on_dev else 0)))
+
+    def add_stereo_view(self, cam: dict, stereo: "Stereo"):
+        """the view with the left rectified image of stereo's last disparity call, from where it lies on the device"""
+        v = fusion_view({**cam, "B": cam.get("B", 0.0)}, stereo.w, stereo.h)
+        self.ctx._chk(self.ctx.lib.sfmx_texture_add_stereo_view(self.ctx.h_, self.h_, byref(v), stereo.h_))
+
+    def view_count(self) -> int:
+        return int(self.ctx.lib.sfmx_texture_view_count(self.h_))
+
+    def set_batch(self, k: int):
+        """k >= 1 forces k views per batch, 0 restores the automatic size; the result does not depend on it"""
+        rc = self.ctx.lib.sfmx_texture_set_batch(self.h_, c_int(int(k)))
+        if rc != SFMX_OK:
+            raise SfmxError(rc, f"sfmx_texture_set_batch: {k} is not in 0 .. {VISIB_MAX_BATCH}")
+
+    def run(self, verts, faces, z_min=0.0, depth_tol=-1.0, n=None, m=None, read=True, **params):
+        """verts float64 [n][3] and faces int32 [m][3]: numpy arrays, or ints (device pointers) with n and m given.  z_min and
+        depth_tol are required; params: TEXTURE_DEFAULTS keys.  Returns read()'s dict, or counts() with read=False."""
+        p = texture_params(z_min, depth_tol, **params)
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int):
+            raise TypeError("verts and faces: both host arrays or both device pointers")
+        if on_dev:
+            pv, pf = c_void_p(verts), c_void_p(faces)
+            n, m = int(n), int(m)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            n, m = len(verts), len(faces)
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+        self.ctx._chk(self.ctx.lib.sfmx_texture_run(self.ctx.h_, self.h_, pv, c_int(n), pf, c_int(m), c_int(1 if on_dev else 0), byref(p)))
+        return self.read() if read else self.counts()
+
+    def sizes(self):
+        """(n, m, V, W, H) of the last successful run; raises before one"""
+        s = [c_int(0) for _ in range(5)]
+        rc = self.ctx.lib.sfmx_texture_sizes(self.h_, *[byref(x) for x in s])
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_texture_sizes: no successful run")
+        return tuple(x.value for x in s)
+
+    def counts(self) -> dict:
+        """dict of TEXTURE_COUNTS of the last successful run; raises before one"""
+        c = (c_int32 * 6)()
+        rc = self.ctx.lib.sfmx_texture_counts(self.h_, c)
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_texture_counts: no successful run")
+        return dict(zip(TEXTURE_COUNTS, [int(x) for x in c]))
+
+    def read(self) -> dict:
+        """the last run: dict(atlas u8 [H][W], face_view i32 [m], face_area i64 [m], uv_half i32 [m][3][2], uv f64 [m][3][2],
+        view_faces i32 [V], the TEXTURE_COUNTS)"""
+        n, m, V, W, H = self.sizes()
+        atlas = np.zeros(max(W * H, 1), np.uint8)
+        fview, farea = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int64)
+        uvh, vfaces = np.zeros((max(m, 1), 3, 2), np.int32), np.zeros(max(V, 1), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_texture_read(self.ctx.h_, self.h_, _p(atlas, c_uint8), _p(fview, c_int32),
+                                                     farea.ctypes.data_as(c_void_p), _p(uvh, c_int32), _p(vfaces, c_int32)))
+        return dict(atlas=atlas[:W * H].reshape(H, W).copy(), face_view=fview[:m].copy(), face_area=farea[:m].copy(), uv_half=uvh[:m].copy(),
+                    uv=texture_uv(uvh[:m], W, H), view_faces=vfaces[:V].copy(), **self.counts())
+
+    def device_atlas(self):
+        """(W H, device pointer of the atlas, W, H); W H = -1 before a successful run"""
+        a, W, H = c_void_p(), c_int(0), c_int(0)
+        k = int(self.ctx.lib.sfmx_texture_device_atlas(self.h_, byref(a), byref(W), byref(H)))
+        return k, a.value, int(W.value), int(H.value)
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_texture_last_us(self.h_))
+
+    def last_bake_us(self) -> float:
+        return float(self.ctx.lib.sfmx_texture_last_bake_us(self.h_))
+
+    def last_batch(self) -> int:
+        """the largest number of views the last run put into one batch"""
+        return int(self.ctx.lib.sfmx_texture_last_batch(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_texture_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Align:
     """sfmx_align: registration of a view to a TSDF volume by direct Gauss-Newton alignment.  The device work
     buffers grow on demand and are kept between calls."""
@@ -2048,6 +2213,9 @@ class Context:
 
     def visib(self) -> "Visib":
         return Visib(self)
+
+    def texture(self) -> "Texture":
+        return Texture(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

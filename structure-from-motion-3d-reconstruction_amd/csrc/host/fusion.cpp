@@ -113,6 +113,14 @@
 #pragma weak sfmx_visib_sizes
 #pragma weak sfmx_visib_counts
 #pragma weak sfmx_visib_device_mesh
+#pragma weak sfmx_texture_check_params
+#pragma weak sfmx_texture_create
+#pragma weak sfmx_texture_destroy
+#pragma weak sfmx_texture_add_stereo_view
+#pragma weak sfmx_texture_run
+#pragma weak sfmx_texture_read
+#pragma weak sfmx_texture_sizes
+#pragma weak sfmx_texture_counts
 
 namespace {
 
@@ -131,7 +139,9 @@ struct Guard {
   sfmx_fill* fl = nullptr;
   sfmx_raster* rs = nullptr;
   sfmx_visib* vb = nullptr;
+  sfmx_texture* tx = nullptr;
   ~Guard() {
+    if (tx) sfmx_texture_destroy(ctx, tx);
     if (vb) sfmx_visib_destroy(ctx, vb);
     if (rs) sfmx_raster_destroy(ctx, rs);
     if (fl) sfmx_fill_destroy(ctx, fl);
@@ -425,6 +435,32 @@ int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
                              sfmx_visib_request* visib, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_tx(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts, gt,
+                                  ev, render, align, simplify, simplify_counts, smooth, smooth_counts, fill, fill_counts, raster, visib, nullptr,
+                                  res, ply_path, warn, warn_cap);
+}
+
+void sfmx_host_texture_free(sfmx_texture_request* texture) {
+  if (!texture) return;
+  std::free(texture->atlas);
+  std::free(texture->face_view);
+  std::free(texture->face_area);
+  std::free(texture->uv_half);
+  std::free(texture->view_faces);
+  texture->atlas = nullptr;
+  texture->face_view = texture->uv_half = texture->view_faces = nullptr;
+  texture->face_area = nullptr;
+}
+
+int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_fusion_result_ex* res, const char* ply_path,
+                             char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -441,6 +477,20 @@ int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on
     vp = visib->params;
     if (vp.depth_tol == 0.0) vp.depth_tol = fp->voxel;
     if (sfmx_visib_check_params(&vp) != SFMX_OK || (visib->colour != 0 && visib->colour != 1) || (visib->colour && !app)) return SFMX_ERR_INVALID;
+  }
+  sfmx_texture_params xp{};
+  if (texture) {
+    for (int32_t& c : texture->counts) c = 0;
+    texture->n_faces = texture->n_views = 0;
+    texture->atlas = nullptr;
+    texture->face_view = texture->uv_half = texture->view_faces = nullptr;
+    texture->face_area = nullptr;
+    if (!&sfmx_texture_check_params || !&sfmx_texture_create || !&sfmx_texture_destroy || !&sfmx_texture_add_stereo_view || !&sfmx_texture_run ||
+        !&sfmx_texture_read || !&sfmx_texture_sizes || !&sfmx_texture_counts)
+      return SFMX_ERR_UNSUPPORTED;
+    xp = texture->params;
+    if (xp.depth_tol == 0.0) xp.depth_tol = fp->voxel;
+    if (sfmx_texture_check_params(&xp) != SFMX_OK) return SFMX_ERR_INVALID;
   }
   if (!&sfmx_fusion_create || !&sfmx_stereo_disparity) return SFMX_ERR_UNSUPPORTED;
   if (app && (!&sfmx_shade_create || !&sfmx_fusion_extract_normals)) return SFMX_ERR_UNSUPPORTED;
@@ -562,6 +612,10 @@ int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on
     rc = sfmx_visib_create(ctx, &g.vb);
     if (rc != SFMX_OK) return rc;
   }
+  if (texture) {
+    rc = sfmx_texture_create(ctx, &g.tx);
+    if (rc != SFMX_OK) return rc;
+  }
   std::vector<int16_t> d16((size_t)w * h);  // sfmx_stereo_disparity always returns the map to the host
   for (int q = 0; q < m; q++) {
     const int a = pairs[2 * q], b = pairs[2 * q + 1];
@@ -618,6 +672,10 @@ int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on
     }
     if (visib) {  // the view as it entered the volume; its left rectified image only when the stage colours
       rc = visib->colour ? sfmx_visib_add_stereo_view(ctx, g.vb, &v, g.st) : sfmx_visib_add_view(ctx, g.vb, &v, nullptr, 0);
+      if (rc != SFMX_OK) return rc;
+    }
+    if (texture) {  // the view as it entered the volume, with its left rectified image
+      rc = sfmx_texture_add_stereo_view(ctx, g.tx, &v, g.st);
       if (rc != SFMX_OK) return rc;
     }
     res->n_views++;
@@ -853,6 +911,7 @@ int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on
       sfmx_host_fusion_free_ex(res);
       res->n_views = keep;
       sfmx_host_visib_free(visib);
+      sfmx_host_texture_free(texture);
       return rc;
     }
     if (nf == 0) {  // nothing left: as a volume without a surface
@@ -876,6 +935,33 @@ int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on
       res->n_faces = nf;
     }
     culled = true;
+  }
+  // the texture is baked for the final mesh, the one in the result arrays and the PLY, fed from those arrays
+  if (texture && nf > 0) {
+    rc = sfmx_texture_run(ctx, g.tx, res->verts, nv, res->faces, nf, 0, &xp);
+    int W = 0, H = 0, V = 0;
+    if (rc == SFMX_OK) rc = sfmx_texture_sizes(g.tx, nullptr, nullptr, &V, &W, &H);
+    if (rc == SFMX_OK) rc = sfmx_texture_counts(g.tx, texture->counts);
+    if (rc == SFMX_OK) {
+      texture->n_faces = nf;
+      texture->n_views = V;
+      texture->atlas = static_cast<uint8_t*>(std::malloc((size_t)W * (size_t)H + 1));
+      texture->face_view = static_cast<int32_t*>(std::malloc((size_t)nf * sizeof(int32_t)));
+      texture->face_area = static_cast<int64_t*>(std::malloc((size_t)nf * sizeof(int64_t)));
+      texture->uv_half = static_cast<int32_t*>(std::malloc((size_t)nf * 6 * sizeof(int32_t)));
+      texture->view_faces = static_cast<int32_t*>(std::malloc((size_t)(V > 0 ? V : 1) * sizeof(int32_t)));
+      if (!texture->atlas || !texture->face_view || !texture->face_area || !texture->uv_half || !texture->view_faces) rc = SFMX_ERR_INVALID;
+    }
+    if (rc == SFMX_OK)
+      rc = sfmx_texture_read(ctx, g.tx, texture->atlas, texture->face_view, texture->face_area, texture->uv_half, texture->view_faces);
+    if (rc != SFMX_OK) {
+      const int keep = res->n_views;
+      sfmx_host_fusion_free_ex(res);
+      res->n_views = keep;
+      sfmx_host_visib_free(visib);
+      sfmx_host_texture_free(texture);
+      return rc;
+    }
   }
   if (gt) {
     // the final mesh is still on the device (inside the simplify or the clean object, or inside the volume after the last
@@ -926,6 +1012,7 @@ int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on
       res->n_views = keep;
       *ev = sfmx_surface_eval_result{};
       sfmx_host_visib_free(visib);
+      sfmx_host_texture_free(texture);
       return rc;
     }
     eval_side(d2, nullptr, gt->params, &ev->n_gt, &ev->comp_within, nullptr, nullptr, nullptr);
@@ -946,6 +1033,7 @@ int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on
       res->n_views = keep;
       if (gt) *ev = sfmx_surface_eval_result{};
       sfmx_host_visib_free(visib);
+      sfmx_host_texture_free(texture);
       return rc;
     }
   }
@@ -971,6 +1059,7 @@ int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on
       res->n_views = keep;
       if (gt) *ev = sfmx_surface_eval_result{};
       sfmx_host_visib_free(visib);
+      sfmx_host_texture_free(texture);
       return rc;
     }
   }

@@ -257,4 +257,31 @@ int sfmx_host_fusion_mesh_vs(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
                              sfmx_visib_request* visib, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_vs with a texture atlas for the final mesh.  texture = NULL: exactly
+// sfmx_host_fusion_mesh_vs.  Otherwise the views are the integrated pairs' left rectified cameras and images (the refined cameras
+// with align), and the stage runs on the final mesh, after the visibility culling when that is asked for; the mesh, every other
+// output and the PLY are what they are without it.  params.depth_tol == 0 stands for the voxel.  The request's outputs are filled:
+// the counts, the faces and views of the run, and atlas u8 [H][W], face_view [n_faces], face_area [n_faces], uv_half
+// [n_faces][3][2], view_faces [n_views] (malloc'ed here, NULL for an empty surface; release them with sfmx_host_texture_free).
+struct sfmx_texture_request {
+  sfmx_texture_params params;
+  int32_t counts[6];  // faces_textured, faces_untextured, cells, W, H, cells_per_row
+  int32_t n_faces, n_views;
+  uint8_t* atlas;
+  int32_t* face_view;
+  int64_t* face_area;
+  int32_t* uv_half;
+  int32_t* view_faces;
+};
+void sfmx_host_texture_free(sfmx_texture_request* texture);
+int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_fusion_result_ex* res, const char* ply_path,
+                             char* warn, int warn_cap);
 }

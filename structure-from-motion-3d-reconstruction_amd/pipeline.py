@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import struct
 from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_ubyte, c_ulonglong, c_void_p
 
 import numpy as np
@@ -234,6 +235,15 @@ class VisibRequest(ctypes.Structure):
                 ("m_in", c_int), ("face_views", POINTER(c_int)), ("face_back_views", POINTER(c_int)), ("vert_views", POINTER(c_int))]
 
 
+TEXTURE_KEYS = ("z_min", "depth_tol", "patch", "cells_per_row", "fill", "obj_path")
+
+
+class TextureRequest(ctypes.Structure):
+    _fields_ = [("params", capi.TextureParams), ("counts", c_int * 6), ("n_faces", c_int), ("n_views", c_int), ("atlas", POINTER(c_ubyte)),
+                ("face_view", POINTER(c_int)), ("face_area", POINTER(ctypes.c_int64)), ("uv_half", POINTER(c_int)),
+                ("view_faces", POINTER(c_int))]
+
+
 ALIGN_KEYS = ("seed", "max_iters", "stride", "min_pixels", "damping", "eps_rot", "eps_trans", "min_weight")
 
 
@@ -248,6 +258,43 @@ def write_pgm(path: str, image) -> None:
     with open(path, "wb") as f:
         f.write(b"P5\n%d %d\n255\n" % (w, h))
         f.write(image.tobytes())
+
+
+def write_bmp(path: str, image) -> None:
+    """a u8 [h][w] image as an uncompressed 8-bit BMP with a grey palette (rows bottom-up, padded to four bytes)"""
+    image = np.ascontiguousarray(image, np.uint8)
+    h, w = image.shape
+    stride = (w + 3) & ~3
+    rows = np.zeros((h, stride), np.uint8)
+    rows[:, :w] = image[::-1]
+    offset = 14 + 40 + 1024
+    with open(path, "wb") as f:
+        f.write(struct.pack("<2sIHHI", b"BM", offset + stride * h, 0, 0, offset))
+        f.write(struct.pack("<IiiHHIIiiII", 40, w, h, 1, 8, 0, stride * h, 2835, 2835, 256, 0))
+        f.write(b"".join(bytes((g, g, g, 0)) for g in range(256)))
+        f.write(rows.tobytes())
+
+
+def write_textured_obj(path: str, verts, faces, uv, atlas) -> None:
+    """NAME.obj (v with %.17g, three vt per face, f a/ta b/tb c/tc), NAME.mtl, NAME_atlas.pgm and NAME_atlas.bmp from path =
+    NAME.obj (or NAME); uv float64 [m][3][2], atlas u8 [H][W]"""
+    stem = path[:-4] if path.lower().endswith(".obj") else path
+    name = os.path.basename(stem)
+    verts = np.asarray(verts, np.float64).reshape(-1, 3)
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
+    uv = np.asarray(uv, np.float64).reshape(-1, 2)
+    atlas = np.ascontiguousarray(atlas, np.uint8)
+    if atlas.size == 0:
+        atlas = np.zeros((1, 1), np.uint8)  # neither format has an empty image
+    write_pgm(stem + "_atlas.pgm", atlas)
+    write_bmp(stem + "_atlas.bmp", atlas)
+    with open(stem + ".mtl", "w") as f:
+        f.write(f"newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 0\nmap_Kd {name}_atlas.bmp\n")
+    with open(stem + ".obj", "w") as f:
+        f.write(f"mtllib {name}.mtl\nusemtl atlas\n")
+        f.write("".join("v %.17g %.17g %.17g\n" % tuple(v) for v in verts))
+        f.write("".join("vt %.17g %.17g\n" % tuple(t) for t in uv))
+        f.write("".join("f %d/%d %d/%d %d/%d\n" % (a + 1, 3 * i + 1, b + 1, 3 * i + 2, c + 1, 3 * i + 3) for i, (a, b, c) in enumerate(faces)))
 
 
 class SurfaceGt(ctypes.Structure):
@@ -294,7 +341,7 @@ def _split_fusion_params(params: dict):
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
          consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, fill=False, raster=None,
-         visibility=False, **params) -> dict:
+         visibility=False, texture=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -351,7 +398,13 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     removed on the device (z_min is required, depth_tol defaults to the voxel) before the mesh is shaded, evaluated,
     rendered by raster and written.  The dict gains visibility = dict(face_views, face_back_views, vert_views (per element of the
     mesh that entered the stage), the capi.VISIB_COUNTS, verts_removed, faces_removed).  colour=True (needs appearance) replaces
-    grey / vertex_views and the PLY colour by this stage's, from the pairs' left rectified images (cull and fill are its)."""
+    grey / vertex_views and the PLY colour by this stage's, from the pairs' left rectified images (cull and fill are its).
+    texture: dict(z_min=, depth_tol=, patch=8, cells_per_row=0, fill=0, obj_path=None) -- the final mesh (after the visibility
+    culling) gets a texture atlas on the device (z_min is required, depth_tol defaults to the voxel): every face takes
+    the integrated pair's left rectified camera that sees it from the front with the largest image area, its patch of the atlas is
+    sampled bilinearly from that pair's left rectified image.  The dict gains texture = dict(atlas u8 [H][W], uv f64 [m][3][2],
+    uv_half, face_view, face_area, view_faces, the capi.TEXTURE_COUNTS).  obj_path = NAME.obj writes NAME.obj, NAME.mtl,
+    NAME_atlas.pgm and NAME_atlas.bmp.  Everything else is what it is without texture."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -496,6 +549,16 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         if vcolour and ap is None:
             raise TypeError("visibility colour=True needs appearance")
         vq = VisibRequest(capi.visib_params(vkw.pop("z_min"), vkw.pop("depth_tol", 0.0), **vkw), int(vcolour))  # 0 = the voxel
+    xq = None
+    if texture:
+        xkw = {} if texture is True else dict(texture)
+        unknown = set(xkw) - set(TEXTURE_KEYS)
+        if unknown:
+            raise TypeError(f"unknown texture parameters {sorted(unknown)}")
+        if "z_min" not in xkw:
+            raise TypeError("texture needs z_min")
+        obj_path = xkw.pop("obj_path", None)
+        xq = TextureRequest(capi.texture_params(xkw.pop("z_min"), xkw.pop("depth_tol", 0.0), **xkw))  # 0 = the voxel
     aq = None
     if align:
         gkw = {} if align is True else dict(align)
@@ -505,12 +568,26 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         seed = int(gkw.pop("seed", 1))
         aouts = (capi.AlignResult * max(len(pr), 1))()
         aq = AlignRequest(seed, capi.align_params(disp_min=fp.disp_min, **gkw), aouts)
-    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None or hp is not None or zq is not None or vq is not None:
+    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None or hp is not None or zq is not None or vq is not None or xq is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if vq is not None:
+        if xq is not None:
+            rc = lib.sfmx_host_fusion_mesh_tx(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None,
+                                              byref(rq) if rq is not None else None, byref(aq) if aq is not None else None,
+                                              byref(mp) if mp is not None else None,
+                                              mcounts.ctypes.data_as(POINTER(c_int)) if mp is not None else None,
+                                              byref(tp) if tp is not None else None,
+                                              tcounts.ctypes.data_as(POINTER(c_int)) if tp is not None else None,
+                                              byref(hp) if hp is not None else None,
+                                              hcounts.ctypes.data_as(POINTER(c_int)) if hp is not None else None,
+                                              byref(zq) if zq is not None else None, byref(vq) if vq is not None else None, byref(xq), *tail)
+        elif vq is not None:
             rc = lib.sfmx_host_fusion_mesh_vs(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -603,6 +680,16 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                            vert_views=np.ctypeslib.as_array(vq.vert_views, (vn,)).astype(np.int32) if vn else np.zeros(0, np.int32),
                            **dict(zip(capi.VISIB_COUNTS, [int(c) for c in vq.counts] + [int(c) for c in vq.pairs])))
                 vis.update(verts_removed=vn - vis["verts_kept"], faces_removed=vm - vis["faces_kept"])
+            if xq is not None:
+                xm, xv = int(xq.n_faces), int(xq.n_views)
+                xc = dict(zip(capi.TEXTURE_COUNTS, [int(c) for c in xq.counts]))
+                xw, xh = xc["W"], xc["H"]
+                tex = dict(atlas=np.ctypeslib.as_array(xq.atlas, (xh, xw)).copy() if xw * xh else np.zeros((0, 0), np.uint8),
+                           face_view=np.ctypeslib.as_array(xq.face_view, (xm,)).astype(np.int32) if xm else np.zeros(0, np.int32),
+                           face_area=np.ctypeslib.as_array(xq.face_area, (xm,)).astype(np.int64) if xm else np.zeros(0, np.int64),
+                           uv_half=np.ctypeslib.as_array(xq.uv_half, (xm, 3, 2)).astype(np.int32) if xm else np.zeros((0, 3, 2), np.int32),
+                           view_faces=np.ctypeslib.as_array(xq.view_faces, (xv,)).astype(np.int32) if xm and xv else np.zeros(xv, np.int32), **xc)
+                tex["uv"] = capi.texture_uv(tex["uv_half"], xw, xh)
             nv, nf = (rex.n_verts, rex.n_faces) if rex.n_faces else (0, 0)
             verts = np.ctypeslib.as_array(rex.verts, (nv, 3)).copy() if nf else np.zeros((0, 3))
             faces = np.ctypeslib.as_array(rex.faces, (nf, 3)).astype(np.int32) if nf else np.zeros((0, 3), np.int32)
@@ -615,8 +702,14 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             lib.sfmx_host_fusion_free_ex(byref(rex))
             if vq is not None:
                 lib.sfmx_host_visib_free(byref(vq))
+            if xq is not None:
+                lib.sfmx_host_texture_free(byref(xq))
         if vq is not None:
             out["visibility"] = vis
+        if xq is not None:
+            out["texture"] = tex
+            if obj_path:
+                write_textured_obj(obj_path, out["verts"], out["faces"], tex["uv"], tex["atlas"])
         if cp is not None:
             done = counts[:len(pr)][counts[:len(pr), 0] >= 0]
             out["consistency"] = dict(valid=[int(v) for v in done[:, 0]], kept=[int(v) for v in done[:, 1]])
@@ -711,7 +804,7 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     pair's view to the volume before it enters it; 'simplify' (True or a dict, as fuse) simplifies the final surface by exact vertex
     clustering; 'smooth' (True or a dict, as fuse) smooths it with the exact Taubin filter first; 'fill' (True or a dict, as fuse) fills its small
     holes before that; 'raster' (a dict, as fuse) renders the final mesh from further cameras; 'visibility' (a dict, as fuse) first removes
-    the faces no pair's camera sees from the front.  The run itself, its log and every other output are unchanged.
+    the faces no pair's camera sees from the front; 'texture' (a dict, as fuse) bakes a texture atlas for the final mesh.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -783,9 +876,10 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         fill = fz.pop("fill", False)
         raster = fz.pop("raster", None)
         visibility = fz.pop("visibility", False)
+        texture = fz.pop("texture", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
                                  appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align,
-                                 simplify=simplify, smooth=smooth, fill=fill, raster=raster, visibility=visibility, **fz)
+                                 simplify=simplify, smooth=smooth, fill=fill, raster=raster, visibility=visibility, texture=texture, **fz)
     return out
 
 

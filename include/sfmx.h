@@ -1008,6 +1008,55 @@ double sfmx_texture_last_bake_us(const sfmx_texture* tx);
 /* the largest number of views the last successful run put into one batch (a property of the schedule, not of the result) */
 int sfmx_texture_last_batch(const sfmx_texture* tx);
 
+/* ---- levelling the seams of a texture atlas: exact per-view vertex offsets ---------------------------------- */
+/* Inputs: a mesh and a sfmx_texture tx whose last successful sfmx_texture_run was on this mesh; that run supplies face_view, the
+ * layout (S = patch, L = S - 2, C, W, H, cells), fill, the views and their images (do not change tx's views in between).
+ * All integer divisions are floor divisions.
+ * Nodes: every corner (f, c) of a textured face (k = face_view[f] >= 0) with vertex v belongs to node (v, k); nodes are the
+ * distinct pairs.  Node sample: graw is the texture's bilinear g (not rounded) in view k at X_r = ((double)L verts[v][r]) /
+ * (double)L, the point of v's corner texel; fx = (int64)floor(graw 256.0 + 0.5), or 256 fill where the texel would be `fill`.
+ * Seam vertices: vertex_views[v] counts the distinct views among v's nodes; v is a seam vertex when it is >= 2, and then
+ * target[v] = (2 sum_k fx(v, k) + c) / (2 c), c = vertex_views[v].  The nodes of a seam vertex are pinned with g = target - fx;
+ * every other node is free and starts at 0.  Neighbours: N(v, k) are the distinct nodes (w, k), w != v, for which a face of
+ * view k has v and w as corners; deg = |N|.  Sweeps (Jacobi), t = 0 .. iterations - 1: every free node gets
+ * g' = (2 sum_N g + deg) / (2 deg), all reads from the values before the sweep; pinned nodes keep theirs.
+ * corner_adj[f][c] = g(node), corner_sample[f][c] = fx(node), both 0 on an untextured face.
+ * Atlas: tx's layout, ownership and fill texels; texel (i, j) of a textured face: i', j', validity and g as the texture's,
+ * N = (L - i' - j') ga + i' gb + j' gc (int64; ga, gb, gc the face's corner_adj),
+ * texel = (u8)min(255, max(0, floor((g + (double)N / (double)(256 L)) + 0.5))).  Nothing is contracted.
+ * Counts, int32: nodes, seam_vertices, pinned_nodes, free_nodes, node_edges (undirected, distinct), iterations.
+ * Every output is bit-identical to the NumPy restatement in tests/level_ref.py whatever the schedule. */
+typedef struct sfmx_level sfmx_level;  /* the work buffers and the last result; they grow and are kept */
+typedef struct sfmx_level_params {
+  int iterations; /* T: Jacobi sweeps, 0 .. 65536 (default 64) */
+} sfmx_level_params;
+void sfmx_level_default_params(sfmx_level_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_level_check_params(const sfmx_level_params* p);
+int sfmx_level_create(sfmx_ctx* ctx, sfmx_level** out);
+void sfmx_level_destroy(sfmx_ctx* ctx, sfmx_level* lv);
+/* verts double [n][3], faces int32 [m][3]: host pointers (copied into the object) or (on_device = 1) device pointers (read in
+ * place; they must stay until the call returns).  SFMX_ERR_INVALID for a tx without a successful run, n or m other than that
+ * run's, a face index outside [0, n) (found on the device without any access through it), 3 m > 2^31 - 1 (decided before any
+ * allocation) and parameters outside their range; the object stays usable and a failed call leaves no result.  m = 0 and a mesh
+ * without a textured face are not errors.  tx and its atlas are not modified. */
+int sfmx_level_run(sfmx_ctx* ctx, sfmx_level* lv, const sfmx_texture* tx, const double* verts, int n, const int32_t* faces, int m,
+                   int on_device, const sfmx_level_params* p);
+/* the last successful run to the host: atlas u8 [H][W], corner_adj int32 [m][3], corner_sample int32 [m][3], vertex_views
+ * int32 [n]; any may be NULL.  SFMX_ERR_INVALID before a successful run. */
+int sfmx_level_read(sfmx_ctx* ctx, sfmx_level* lv, uint8_t* atlas, int32_t* corner_adj, int32_t* corner_sample, int32_t* vertex_views);
+/* counts6 int32 [6] = nodes, seam_vertices, pinned_nodes, free_nodes, node_edges, iterations.  SFMX_ERR_INVALID (and zeros)
+ * before a successful run. */
+int sfmx_level_counts(const sfmx_level* lv, int32_t* counts6);
+/* the levelled atlas on the device, the object's own array; any pointer may be NULL.  Returns W H, or -1 before a successful
+ * run.  Valid until the next run on lv. */
+int sfmx_level_device_atlas(const sfmx_level* lv, const uint8_t** atlas, int* W, int* H);
+/* device time (us) from the first to the last launch of the last run, of the sweeps alone and of the bake kernel alone, when
+ * timing is on (sfmx_set_timing), else 0 */
+double sfmx_level_last_us(const sfmx_level* lv);
+double sfmx_level_last_sweeps_us(const sfmx_level* lv);
+double sfmx_level_last_bake_us(const sfmx_level* lv);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

@@ -70,6 +70,9 @@ SYMBOLS = [
     "sfmx_texture_add_view", "sfmx_texture_add_stereo_view", "sfmx_texture_view_count", "sfmx_texture_set_batch", "sfmx_texture_run",
     "sfmx_texture_read", "sfmx_texture_sizes", "sfmx_texture_counts", "sfmx_texture_device_atlas", "sfmx_texture_last_us",
     "sfmx_texture_last_bake_us", "sfmx_texture_last_batch",
+    "sfmx_level_default_params", "sfmx_level_check_params", "sfmx_level_create", "sfmx_level_destroy", "sfmx_level_run",
+    "sfmx_level_read", "sfmx_level_counts", "sfmx_level_device_atlas", "sfmx_level_last_us", "sfmx_level_last_sweeps_us",
+    "sfmx_level_last_bake_us",
 ]
 
 
@@ -491,6 +494,36 @@ def texture_uv(uv_half, W, H):
     return out
 
 
+class LevelParams(ctypes.Structure):
+    _fields_ = [("iterations", c_int)]
+
+
+LEVEL_DEFAULTS = dict(iterations=64)
+LEVEL_COUNTS = ("nodes", "seam_vertices", "pinned_nodes", "free_nodes", "node_edges", "iterations")
+
+
+def level_params(**kw) -> LevelParams:
+    unknown = set(kw) - set(LEVEL_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown level parameters {sorted(unknown)}")
+    kw = {**LEVEL_DEFAULTS, **kw}
+    if int(kw["iterations"]) != kw["iterations"]:
+        raise TypeError("level parameter iterations is an integer")
+    return LevelParams(int(kw["iterations"]))
+
+
+def level_default_params() -> dict:
+    """sfmx_level_default_params as a dict (needs no device)"""
+    p = LevelParams()
+    load_library().sfmx_level_default_params(byref(p))
+    return {k: getattr(p, k) for k, _ in LevelParams._fields_}
+
+
+def level_check_params(**kw) -> bool:
+    """True if sfmx_level_run would accept the parameters; needs no device"""
+    return load_library().sfmx_level_check_params(byref(level_params(**kw))) == SFMX_OK
+
+
 ALIGN_ITERS_CAP = 64  # SFMX_ALIGN_ITERS_CAP
 ALIGN_CONVERGED, ALIGN_MAX_ITERS, ALIGN_TOO_FEW, ALIGN_DEGENERATE = range(4)
 ALIGN_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")
@@ -582,6 +615,9 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_visib_last_us.restype = c_double
         _lib.sfmx_texture_last_us.restype = c_double
         _lib.sfmx_texture_last_bake_us.restype = c_double
+        _lib.sfmx_level_last_us.restype = c_double
+        _lib.sfmx_level_last_sweeps_us.restype = c_double
+        _lib.sfmx_level_last_bake_us.restype = c_double
     return _lib
 
 
@@ -1764,6 +1800,86 @@ class Texture:
             pass
 
 
+class Level:
+    """sfmx_level: the seams of a texture atlas levelled: one offset per (vertex, view), pinned to the mean of the
+    views' samples on the seams and relaxed by Jacobi sweeps elsewhere, added to every texel of the texture object's atlas before
+    its rounding.  The work buffers are kept between runs."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        self.n_ = self.m_ = 0
+        ctx._chk(ctx.lib.sfmx_level_create(ctx.h_, byref(self.h_)))
+
+    def run(self, tx: "Texture", verts, faces, n=None, m=None, read=True, **params):
+        """tx: the Texture whose last run was on this mesh.  verts float64 [n][3] and faces int32 [m][3]: numpy arrays, or ints
+        (device pointers) with n and m given.  params: LEVEL_DEFAULTS keys.  Returns read()'s dict, or counts() with read=False."""
+        p = level_params(**params)
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int):
+            raise TypeError("verts and faces: both host arrays or both device pointers")
+        if on_dev:
+            pv, pf = c_void_p(verts), c_void_p(faces)
+            n, m = int(n), int(m)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            n, m = len(verts), len(faces)
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+        self.ctx._chk(self.ctx.lib.sfmx_level_run(self.ctx.h_, self.h_, tx.h_, pv, c_int(n), pf, c_int(m), c_int(1 if on_dev else 0), byref(p)))
+        self.n_, self.m_ = n, m
+        return self.read() if read else self.counts()
+
+    def counts(self) -> dict:
+        """dict of LEVEL_COUNTS of the last successful run; raises before one"""
+        c = (c_int32 * 6)()
+        rc = self.ctx.lib.sfmx_level_counts(self.h_, c)
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_level_counts: no successful run")
+        return dict(zip(LEVEL_COUNTS, [int(x) for x in c]))
+
+    def read(self) -> dict:
+        """the last run: dict(atlas u8 [H][W], corner_adj i32 [m][3], corner_sample i32 [m][3], vertex_views i32 [n], the
+        LEVEL_COUNTS)"""
+        k, _, W, H = self.device_atlas()
+        if k < 0:
+            raise SfmxError(SFMX_ERR_INVALID, "sfmx_level_read: no successful run")
+        n, m = self.n_, self.m_
+        atlas = np.zeros(max(W * H, 1), np.uint8)
+        cadj, csamp = np.zeros((max(m, 1), 3), np.int32), np.zeros((max(m, 1), 3), np.int32)
+        vviews = np.zeros(max(n, 1), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_level_read(self.ctx.h_, self.h_, _p(atlas, c_uint8), _p(cadj, c_int32), _p(csamp, c_int32),
+                                                   _p(vviews, c_int32)))
+        return dict(atlas=atlas[:W * H].reshape(H, W).copy(), corner_adj=cadj[:m].copy(), corner_sample=csamp[:m].copy(),
+                    vertex_views=vviews[:n].copy(), **self.counts())
+
+    def device_atlas(self):
+        """(W H, device pointer of the levelled atlas, W, H); W H = -1 before a successful run"""
+        a, W, H = c_void_p(), c_int(0), c_int(0)
+        k = int(self.ctx.lib.sfmx_level_device_atlas(self.h_, byref(a), byref(W), byref(H)))
+        return k, a.value, int(W.value), int(H.value)
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_level_last_us(self.h_))
+
+    def last_sweeps_us(self) -> float:
+        return float(self.ctx.lib.sfmx_level_last_sweeps_us(self.h_))
+
+    def last_bake_us(self) -> float:
+        return float(self.ctx.lib.sfmx_level_last_bake_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_level_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Align:
     """sfmx_align: registration of a view to a TSDF volume by direct Gauss-Newton alignment.  The device work
     buffers grow on demand and are kept between calls."""
@@ -2216,6 +2332,9 @@ class Context:
 
     def texture(self) -> "Texture":
         return Texture(self)
+
+    def level(self) -> "Level":
+        return Level(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

@@ -35,6 +35,7 @@
 
 #include "sfmx_internal.h"
 #include "sfmx_raster_dev.h"
+#include "sfmx_texture_dev.h"
 
 namespace {
 
@@ -132,10 +133,6 @@ __global__ __launch_bounds__(256) void k_tx_list(int m, const int* __restrict__ 
   list[rank[f]] = f;
   atomicAdd(&view_faces[k], 1);  // integers: the order does not matter
 }
-
-struct TxLayout {
-  int S, C, cells, n_tex, fill_cell, W, H, fill;  // fill_cell: its index, or -1 without one
-};
 
 __global__ __launch_bounds__(256) void k_tx_bake(const double* __restrict__ verts, const int* __restrict__ faces,
                                                  const int* __restrict__ list, const int* __restrict__ fview,
@@ -248,24 +245,6 @@ struct TxBatch {
 };
 
 }  // namespace
-
-struct sfmx_texture {
-  std::vector<sfmx_fusion_view> views;
-  std::vector<long long> img_off;  // of a view's image in the image slab, -1 without one
-  std::vector<RsSlot> slots;       // of the last run, as uploaded
-  long long img_used = 0;
-  int forced_batch = 0, last_batch = 0;
-  DevBuf img, d_slots;
-  DevBuf keys, pv, fl, big, rcounters;      // one batch's z-buffers
-  DevBuf work;                              // masks, flags, ranks, the list, the scan's partials
-  DevBuf res;                               // the words
-  DevBuf in_v, in_f;                        // host inputs, staged
-  DevBuf fview, farea, uvh, vfaces, atlas;  // the result
-  bool done = false;
-  int n = 0, m = 0, nviews = 0;
-  int32_t counts[6] = {};
-  StageTimer t, tb;  // the whole run, k_tx_bake alone
-};
 
 namespace {
 
@@ -425,6 +404,7 @@ int tx_run(sfmx_ctx* ctx, sfmx_texture* tx, const double* verts, int n, const in
   tx->counts[3] = lay.W;
   tx->counts[4] = lay.H;
   tx->counts[5] = lay.C;
+  tx->lay = lay;
   tx->last_batch = widest;
   tx->done = true;
   return SFMX_OK;

@@ -121,6 +121,12 @@
 #pragma weak sfmx_texture_read
 #pragma weak sfmx_texture_sizes
 #pragma weak sfmx_texture_counts
+#pragma weak sfmx_level_check_params
+#pragma weak sfmx_level_create
+#pragma weak sfmx_level_destroy
+#pragma weak sfmx_level_run
+#pragma weak sfmx_level_read
+#pragma weak sfmx_level_counts
 
 namespace {
 
@@ -140,7 +146,9 @@ struct Guard {
   sfmx_raster* rs = nullptr;
   sfmx_visib* vb = nullptr;
   sfmx_texture* tx = nullptr;
+  sfmx_level* lv = nullptr;
   ~Guard() {
+    if (lv) sfmx_level_destroy(ctx, lv);
     if (tx) sfmx_texture_destroy(ctx, tx);
     if (vb) sfmx_visib_destroy(ctx, vb);
     if (rs) sfmx_raster_destroy(ctx, rs);
@@ -461,6 +469,30 @@ int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
                              sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_fusion_result_ex* res, const char* ply_path,
                              char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_lv(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts, gt,
+                                  ev, render, align, simplify, simplify_counts, smooth, smooth_counts, fill, fill_counts, raster, visib, texture,
+                                  nullptr, res, ply_path, warn, warn_cap);
+}
+
+void sfmx_host_level_free(sfmx_level_request* level) {
+  if (!level) return;
+  std::free(level->atlas);
+  std::free(level->corner_adj);
+  std::free(level->corner_sample);
+  std::free(level->vertex_views);
+  level->atlas = nullptr;
+  level->corner_adj = level->corner_sample = level->vertex_views = nullptr;
+}
+
+int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_level_request* level, sfmx_fusion_result_ex* res,
+                             const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -491,6 +523,15 @@ int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on
     xp = texture->params;
     if (xp.depth_tol == 0.0) xp.depth_tol = fp->voxel;
     if (sfmx_texture_check_params(&xp) != SFMX_OK) return SFMX_ERR_INVALID;
+  }
+  if (level) {
+    for (int32_t& c : level->counts) c = 0;
+    level->n_faces = level->n_verts = 0;
+    level->atlas = nullptr;
+    level->corner_adj = level->corner_sample = level->vertex_views = nullptr;
+    if (!&sfmx_level_check_params || !&sfmx_level_create || !&sfmx_level_destroy || !&sfmx_level_run || !&sfmx_level_read || !&sfmx_level_counts)
+      return SFMX_ERR_UNSUPPORTED;
+    if (!texture || sfmx_level_check_params(&level->params) != SFMX_OK) return SFMX_ERR_INVALID;
   }
   if (!&sfmx_fusion_create || !&sfmx_stereo_disparity) return SFMX_ERR_UNSUPPORTED;
   if (app && (!&sfmx_shade_create || !&sfmx_fusion_extract_normals)) return SFMX_ERR_UNSUPPORTED;
@@ -614,6 +655,10 @@ int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on
   }
   if (texture) {
     rc = sfmx_texture_create(ctx, &g.tx);
+    if (rc != SFMX_OK) return rc;
+  }
+  if (level) {
+    rc = sfmx_level_create(ctx, &g.lv);
     if (rc != SFMX_OK) return rc;
   }
   std::vector<int16_t> d16((size_t)w * h);  // sfmx_stereo_disparity always returns the map to the host
@@ -912,6 +957,7 @@ int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on
       res->n_views = keep;
       sfmx_host_visib_free(visib);
       sfmx_host_texture_free(texture);
+      sfmx_host_level_free(level);
       return rc;
     }
     if (nf == 0) {  // nothing left: as a volume without a surface
@@ -954,12 +1000,28 @@ int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on
     }
     if (rc == SFMX_OK)
       rc = sfmx_texture_read(ctx, g.tx, texture->atlas, texture->face_view, texture->face_area, texture->uv_half, texture->view_faces);
+    // the seams are levelled on the same mesh, from the texture object as the run left it
+    if (rc == SFMX_OK && level) {
+      rc = sfmx_level_run(ctx, g.lv, g.tx, res->verts, nv, res->faces, nf, 0, &level->params);
+      if (rc == SFMX_OK) rc = sfmx_level_counts(g.lv, level->counts);
+      if (rc == SFMX_OK) {
+        level->n_faces = nf;
+        level->n_verts = nv;
+        level->atlas = static_cast<uint8_t*>(std::malloc((size_t)W * (size_t)H + 1));
+        level->corner_adj = static_cast<int32_t*>(std::malloc((size_t)nf * 3 * sizeof(int32_t)));
+        level->corner_sample = static_cast<int32_t*>(std::malloc((size_t)nf * 3 * sizeof(int32_t)));
+        level->vertex_views = static_cast<int32_t*>(std::malloc((size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
+        if (!level->atlas || !level->corner_adj || !level->corner_sample || !level->vertex_views) rc = SFMX_ERR_INVALID;
+      }
+      if (rc == SFMX_OK) rc = sfmx_level_read(ctx, g.lv, level->atlas, level->corner_adj, level->corner_sample, level->vertex_views);
+    }
     if (rc != SFMX_OK) {
       const int keep = res->n_views;
       sfmx_host_fusion_free_ex(res);
       res->n_views = keep;
       sfmx_host_visib_free(visib);
       sfmx_host_texture_free(texture);
+      sfmx_host_level_free(level);
       return rc;
     }
   }
@@ -1013,6 +1075,7 @@ int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on
       *ev = sfmx_surface_eval_result{};
       sfmx_host_visib_free(visib);
       sfmx_host_texture_free(texture);
+      sfmx_host_level_free(level);
       return rc;
     }
     eval_side(d2, nullptr, gt->params, &ev->n_gt, &ev->comp_within, nullptr, nullptr, nullptr);
@@ -1034,6 +1097,7 @@ int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on
       if (gt) *ev = sfmx_surface_eval_result{};
       sfmx_host_visib_free(visib);
       sfmx_host_texture_free(texture);
+      sfmx_host_level_free(level);
       return rc;
     }
   }
@@ -1060,6 +1124,7 @@ int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on
       if (gt) *ev = sfmx_surface_eval_result{};
       sfmx_host_visib_free(visib);
       sfmx_host_texture_free(texture);
+      sfmx_host_level_free(level);
       return rc;
     }
   }

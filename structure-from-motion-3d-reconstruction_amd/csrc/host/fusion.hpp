@@ -284,4 +284,30 @@ int sfmx_host_fusion_mesh_tx(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
                              sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_fusion_result_ex* res, const char* ply_path,
                              char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_tx with the atlas's seams levelled.  level = NULL: exactly sfmx_host_fusion_mesh_tx.
+// Otherwise a texture request is required (SFMX_ERR_INVALID without one); the level stage runs after the texture stage on the
+// same final mesh, and the mesh, the texture request's outputs, every other output and the PLY are what they are without it.
+// The request's outputs are filled: the counts, the faces and vertices of the run, and atlas u8 [H][W] (the texture request's W
+// and H), corner_adj [n_faces][3], corner_sample [n_faces][3], vertex_views [n_verts] (malloc'ed here, NULL for an empty
+// surface; release them with sfmx_host_level_free).
+struct sfmx_level_request {
+  sfmx_level_params params;
+  int32_t counts[6];  // nodes, seam_vertices, pinned_nodes, free_nodes, node_edges, iterations
+  int32_t n_faces, n_verts;
+  uint8_t* atlas;
+  int32_t* corner_adj;
+  int32_t* corner_sample;
+  int32_t* vertex_views;
+};
+void sfmx_host_level_free(sfmx_level_request* level);
+int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_level_request* level, sfmx_fusion_result_ex* res,
+                             const char* ply_path, char* warn, int warn_cap);
 }

@@ -244,6 +244,14 @@ class TextureRequest(ctypes.Structure):
                 ("view_faces", POINTER(c_int))]
 
 
+LEVEL_KEYS = ("iterations",)
+
+
+class LevelRequest(ctypes.Structure):
+    _fields_ = [("params", capi.LevelParams), ("counts", c_int * 6), ("n_faces", c_int), ("n_verts", c_int), ("atlas", POINTER(c_ubyte)),
+                ("corner_adj", POINTER(c_int)), ("corner_sample", POINTER(c_int)), ("vertex_views", POINTER(c_int))]
+
+
 ALIGN_KEYS = ("seed", "max_iters", "stride", "min_pixels", "damping", "eps_rot", "eps_trans", "min_weight")
 
 
@@ -341,7 +349,7 @@ def _split_fusion_params(params: dict):
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
          consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, fill=False, raster=None,
-         visibility=False, texture=False, **params) -> dict:
+         visibility=False, texture=False, level=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -404,7 +412,12 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     the integrated pair's left rectified camera that sees it from the front with the largest image area, its patch of the atlas is
     sampled bilinearly from that pair's left rectified image.  The dict gains texture = dict(atlas u8 [H][W], uv f64 [m][3][2],
     uv_half, face_view, face_area, view_faces, the capi.TEXTURE_COUNTS).  obj_path = NAME.obj writes NAME.obj, NAME.mtl,
-    NAME_atlas.pgm and NAME_atlas.bmp.  Everything else is what it is without texture."""
+    NAME_atlas.pgm and NAME_atlas.bmp.  Everything else is what it is without texture.
+    level: True, or dict(iterations=64) (needs texture) -- the atlas's seams are levelled on the device: every (vertex,
+    view) of a textured face gets an offset in 1/256 grey level, pinned on the vertices where views meet to the mean of the views'
+    samples and relaxed elsewhere by `iterations` Jacobi sweeps, and every texel gets the blend of its face's three offsets before
+    its rounding.  The dict gains level = dict(atlas u8 [H][W], corner_adj i32 [m][3], corner_sample i32 [m][3], vertex_views i32
+    [n], the capi.LEVEL_COUNTS); texture is unchanged, and with obj_path the written atlas files are the levelled atlas."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -559,6 +572,15 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             raise TypeError("texture needs z_min")
         obj_path = xkw.pop("obj_path", None)
         xq = TextureRequest(capi.texture_params(xkw.pop("z_min"), xkw.pop("depth_tol", 0.0), **xkw))  # 0 = the voxel
+    lq = None
+    if level:
+        lkw = {} if level is True else dict(level)
+        unknown = set(lkw) - set(LEVEL_KEYS)
+        if unknown:
+            raise TypeError(f"unknown level parameters {sorted(unknown)}")
+        if xq is None:
+            raise TypeError("level needs texture")
+        lq = LevelRequest(capi.level_params(**lkw))
     aq = None
     if align:
         gkw = {} if align is True else dict(align)
@@ -573,7 +595,21 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if xq is not None:
+        if lq is not None:
+            rc = lib.sfmx_host_fusion_mesh_lv(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None,
+                                              byref(rq) if rq is not None else None, byref(aq) if aq is not None else None,
+                                              byref(mp) if mp is not None else None,
+                                              mcounts.ctypes.data_as(POINTER(c_int)) if mp is not None else None,
+                                              byref(tp) if tp is not None else None,
+                                              tcounts.ctypes.data_as(POINTER(c_int)) if tp is not None else None,
+                                              byref(hp) if hp is not None else None,
+                                              hcounts.ctypes.data_as(POINTER(c_int)) if hp is not None else None,
+                                              byref(zq) if zq is not None else None, byref(vq) if vq is not None else None, byref(xq), byref(lq), *tail)
+        elif xq is not None:
             rc = lib.sfmx_host_fusion_mesh_tx(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -690,6 +726,13 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                            uv_half=np.ctypeslib.as_array(xq.uv_half, (xm, 3, 2)).astype(np.int32) if xm else np.zeros((0, 3, 2), np.int32),
                            view_faces=np.ctypeslib.as_array(xq.view_faces, (xv,)).astype(np.int32) if xm and xv else np.zeros(xv, np.int32), **xc)
                 tex["uv"] = capi.texture_uv(tex["uv_half"], xw, xh)
+            if lq is not None:
+                qm, qn = int(lq.n_faces), int(lq.n_verts)
+                lev = dict(atlas=np.ctypeslib.as_array(lq.atlas, (xh, xw)).copy() if qm and xw * xh else np.zeros((xh, xw) if qm else (0, 0), np.uint8),
+                           corner_adj=np.ctypeslib.as_array(lq.corner_adj, (qm, 3)).astype(np.int32) if qm else np.zeros((0, 3), np.int32),
+                           corner_sample=np.ctypeslib.as_array(lq.corner_sample, (qm, 3)).astype(np.int32) if qm else np.zeros((0, 3), np.int32),
+                           vertex_views=np.ctypeslib.as_array(lq.vertex_views, (qn,)).astype(np.int32) if qm and qn else np.zeros(qn, np.int32),
+                           **dict(zip(capi.LEVEL_COUNTS, [int(c) for c in lq.counts])))
             nv, nf = (rex.n_verts, rex.n_faces) if rex.n_faces else (0, 0)
             verts = np.ctypeslib.as_array(rex.verts, (nv, 3)).copy() if nf else np.zeros((0, 3))
             faces = np.ctypeslib.as_array(rex.faces, (nf, 3)).astype(np.int32) if nf else np.zeros((0, 3), np.int32)
@@ -704,12 +747,16 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                 lib.sfmx_host_visib_free(byref(vq))
             if xq is not None:
                 lib.sfmx_host_texture_free(byref(xq))
+            if lq is not None:
+                lib.sfmx_host_level_free(byref(lq))
         if vq is not None:
             out["visibility"] = vis
         if xq is not None:
             out["texture"] = tex
+            if lq is not None:
+                out["level"] = lev
             if obj_path:
-                write_textured_obj(obj_path, out["verts"], out["faces"], tex["uv"], tex["atlas"])
+                write_textured_obj(obj_path, out["verts"], out["faces"], tex["uv"], lev["atlas"] if lq is not None else tex["atlas"])
         if cp is not None:
             done = counts[:len(pr)][counts[:len(pr), 0] >= 0]
             out["consistency"] = dict(valid=[int(v) for v in done[:, 0]], kept=[int(v) for v in done[:, 1]])
@@ -804,7 +851,7 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     pair's view to the volume before it enters it; 'simplify' (True or a dict, as fuse) simplifies the final surface by exact vertex
     clustering; 'smooth' (True or a dict, as fuse) smooths it with the exact Taubin filter first; 'fill' (True or a dict, as fuse) fills its small
     holes before that; 'raster' (a dict, as fuse) renders the final mesh from further cameras; 'visibility' (a dict, as fuse) first removes
-    the faces no pair's camera sees from the front; 'texture' (a dict, as fuse) bakes a texture atlas for the final mesh.  The run itself, its log and every other output are unchanged.
+    the faces no pair's camera sees from the front; 'texture' (a dict, as fuse) bakes a texture atlas for the final mesh; 'level' (True or a dict, as fuse, with texture) levels its seams.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -877,9 +924,11 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         raster = fz.pop("raster", None)
         visibility = fz.pop("visibility", False)
         texture = fz.pop("texture", False)
+        level = fz.pop("level", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
                                  appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align,
-                                 simplify=simplify, smooth=smooth, fill=fill, raster=raster, visibility=visibility, texture=texture, **fz)
+                                 simplify=simplify, smooth=smooth, fill=fill, raster=raster, visibility=visibility, texture=texture,
+                                 level=level, **fz)
     return out
 
 

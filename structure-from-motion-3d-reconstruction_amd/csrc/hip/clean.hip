@@ -18,11 +18,11 @@
 //   k_cl_mark        per face: the keep rule on cf[lab[v0]]; a kept face flags its three corners
 //   k_scan_*         exclusive int32 scans of the face flags and the vertex flags, one launch per level (scan.hip: no
 //                    hand-off between workgroups inside a launch)
-//   k_cl_emit_verts  per kept vertex: its 24 bytes (and its normal's), its input index
-//   k_cl_emit_faces  per kept face: its renumbered indices, its input index
+//   k_mesh_emit_*    the kept vertices and the renumbered kept faces (sfmx_mesh_dev.h: MeshCompact, shared with visib.hip)
 // No kernel waits on another workgroup or spins on a memory word.  A face with an index out of range is skipped by every
 // per-face kernel (they all run before the host reads the flag), so nothing is ever accessed through such an index.
 #include "sfmx_internal.h"
+#include "sfmx_mesh_dev.h"
 
 namespace {
 
@@ -52,13 +52,6 @@ __device__ __forceinline__ void cl_unite(int* lab, int a, int b) {
   }
 }
 
-__device__ __forceinline__ bool cl_face(const int* __restrict__ faces, int f, int n, int& v0, int& v1, int& v2) {
-  v0 = faces[3 * (size_t)f];
-  v1 = faces[3 * (size_t)f + 1];
-  v2 = faces[3 * (size_t)f + 2];
-  return (unsigned)v0 < (unsigned)n && (unsigned)v1 < (unsigned)n && (unsigned)v2 < (unsigned)n;
-}
-
 __global__ __launch_bounds__(256) void k_cl_init(int n, int* __restrict__ lab, int* __restrict__ cf, int* __restrict__ vkeep) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= n) return;
@@ -71,7 +64,7 @@ __global__ __launch_bounds__(256) void k_cl_merge(const int* __restrict__ faces,
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= m) return;
   int v0, v1, v2;
-  if (!cl_face(faces, f, n, v0, v1, v2)) {
+  if (!mesh_face(faces, f, n, v0, v1, v2)) {
     atomicOr(&counters[CL_FLAG], 1);
     return;
   }
@@ -90,7 +83,7 @@ __global__ __launch_bounds__(256) void k_cl_count(const int* __restrict__ faces,
                                                   int* __restrict__ cf) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   int v0, v1, v2;
-  const int r = f < m && cl_face(faces, f, n, v0, v1, v2) ? lab[v0] : -1;
+  const int r = f < m && mesh_face(faces, f, n, v0, v1, v2) ? lab[v0] : -1;
   // one atomicAdd per wave and root: nearly every face of a surface belongs to one component, and a million adds on one
   // word are served one after the other.  The loop runs on wave-uniform values; nothing is read from memory inside it.
   const int lane = threadIdx.x & 63;
@@ -132,7 +125,7 @@ __global__ __launch_bounds__(256) void k_cl_mark(const int* __restrict__ faces, 
   if (f >= m) return;
   int v0, v1, v2;
   bool keep = false;
-  if (cl_face(faces, f, n, v0, v1, v2)) {
+  if (mesh_face(faces, f, n, v0, v1, v2)) {
     const int c = cf[lab[v0]];
     keep = c >= 1 && c >= min_faces && (long long)c * 1000 >= (long long)counters[CL_LARGEST] * min_permille;
   }
@@ -144,44 +137,16 @@ __global__ __launch_bounds__(256) void k_cl_mark(const int* __restrict__ faces, 
   }
 }
 
-__global__ __launch_bounds__(256) void k_cl_emit_verts(int n, const int* __restrict__ vkeep, const int* __restrict__ voff,
-                                                       const unsigned long long* __restrict__ verts,
-                                                       const unsigned long long* __restrict__ normals,
-                                                       unsigned long long* __restrict__ verts_out,
-                                                       unsigned long long* __restrict__ normals_out, int* __restrict__ vsrc) {
-  const int v = blockIdx.x * 256 + threadIdx.x;
-  if (v >= n || !vkeep[v]) return;
-  const size_t o = (size_t)voff[v], i = (size_t)v;
-#pragma unroll
-  for (int a = 0; a < 3; a++) verts_out[3 * o + a] = verts[3 * i + a];
-  if (normals) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) normals_out[3 * o + a] = normals[3 * i + a];
-  }
-  vsrc[o] = v;
-}
-
-__global__ __launch_bounds__(256) void k_cl_emit_faces(const int* __restrict__ faces, int m, const int* __restrict__ fkeep,
-                                                       const int* __restrict__ foff, const int* __restrict__ voff,
-                                                       int* __restrict__ faces_out, int* __restrict__ fsrc) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f >= m || !fkeep[f]) return;  // a kept face has passed the range check
-  const size_t o = (size_t)foff[f];
-#pragma unroll
-  for (int a = 0; a < 3; a++) faces_out[3 * o + a] = voff[faces[3 * (size_t)f + a]];
-  fsrc[o] = f;
-}
-
 }  // namespace
 
 struct sfmx_clean {
   // per input vertex: lab, cf, vcf, vkeep, voff; per input face: fkeep, foff; then the scans' partials and the counters
   DevBuf work;
-  DevBuf in_v, in_n, in_f;  // host inputs, staged
-  DevBuf out_v, out_n, out_f, vsrc, fsrc;
+  MeshInput in;     // host inputs, staged
+  MeshCompact out;  // the cleaned mesh
   int *lab = nullptr, *vcf = nullptr;  // into work, of the last successful run
-  bool done = false, has_normals = false;
-  int n = 0, m = 0, nv_out = 0, nf_out = 0;
+  bool done = false;
+  int n = 0, m = 0;
   StageTimer t;
 };
 
@@ -196,12 +161,7 @@ int cl_run(sfmx_ctx* ctx, sfmx_clean* cl, const double* verts, const double* nor
   const size_t nn = (size_t)n, mm = (size_t)m;
   const size_t aux = sfmx_scan_aux(n > m ? n : m);
   SFMX_HIP(ctx, cl->work.ensure((5 * nn + 2 * mm + aux + CL_COUNTERS) * 4));
-  // the outputs are sized by the input: the kept counts are only known on the host after the launches
-  SFMX_HIP(ctx, cl->out_v.ensure(nn * 24));
-  if (normals) SFMX_HIP(ctx, cl->out_n.ensure(nn * 24));
-  SFMX_HIP(ctx, cl->out_f.ensure(mm * 12));
-  SFMX_HIP(ctx, cl->vsrc.ensure(nn * 4));
-  SFMX_HIP(ctx, cl->fsrc.ensure(mm * 4));
+  SFMX_HIP(ctx, cl->out.ensure(nn, mm, normals != nullptr));
   int* lab = cl->work.as<int>();
   int* cf = lab + nn;
   int* vcf = cf + nn;
@@ -219,19 +179,8 @@ int cl_run(sfmx_ctx* ctx, sfmx_clean* cl, const double* verts, const double* nor
   if (n > 0) k_cl_flatten<<<nbv, 256, 0, s>>>(n, lab);
   if (m > 0) k_cl_count<<<nbf, 256, 0, s>>>(faces, m, n, lab, cf);
   if (n > 0) k_cl_stats<<<nbv, 256, 0, s>>>(n, lab, cf, vcf, counters);
-  if (m > 0) {
-    k_cl_mark<<<nbf, 256, 0, s>>>(faces, m, n, lab, cf, counters, p->min_faces, p->min_permille, fkeep, vkeep);
-    sfmx_scan(fkeep, false, m, foff, ax, s);
-    sfmx_scan_total(fkeep, false, foff, m, counters + CL_NF_OUT, s);
-  }
-  if (n > 0) {
-    sfmx_scan(vkeep, false, n, voff, ax, s);
-    sfmx_scan_total(vkeep, false, voff, n, counters + CL_NV_OUT, s);
-    k_cl_emit_verts<<<nbv, 256, 0, s>>>(n, vkeep, voff, reinterpret_cast<const unsigned long long*>(verts),
-                                        reinterpret_cast<const unsigned long long*>(normals), cl->out_v.as<unsigned long long>(),
-                                        cl->out_n.as<unsigned long long>(), cl->vsrc.as<int>());
-  }
-  if (m > 0) k_cl_emit_faces<<<nbf, 256, 0, s>>>(faces, m, fkeep, foff, voff, cl->out_f.as<int>(), cl->fsrc.as<int>());
+  if (m > 0) k_cl_mark<<<nbf, 256, 0, s>>>(faces, m, n, lab, cf, counters, p->min_faces, p->min_permille, fkeep, vkeep);
+  cl->out.launch(verts, normals, n, faces, m, fkeep, foff, vkeep, voff, ax, counters + CL_NF_OUT, counters + CL_NV_OUT, m > 0, s);
   SFMX_HIP(ctx, hipGetLastError());
   SFMX_HIP(ctx, cl->t.end(ctx));
   int c[CL_COUNTERS] = {};
@@ -243,12 +192,12 @@ int cl_run(sfmx_ctx* ctx, sfmx_clean* cl, const double* verts, const double* nor
   cl->vcf = vcf;
   cl->n = n;
   cl->m = m;
-  cl->nv_out = c[CL_NV_OUT];
-  cl->nf_out = c[CL_NF_OUT];
-  cl->has_normals = normals != nullptr;
+  cl->out.nv_out = c[CL_NV_OUT];
+  cl->out.nf_out = c[CL_NF_OUT];
+  cl->out.has_normals = normals != nullptr;
   cl->done = true;
-  if (n_verts_out) *n_verts_out = cl->nv_out;
-  if (n_faces_out) *n_faces_out = cl->nf_out;
+  if (n_verts_out) *n_verts_out = cl->out.nv_out;
+  if (n_faces_out) *n_faces_out = cl->out.nf_out;
   if (n_components) *n_components = c[CL_NCOMP];
   if (largest) *largest = c[CL_LARGEST];
   return SFMX_OK;
@@ -296,7 +245,9 @@ void sfmx_clean_destroy(sfmx_ctx* ctx, sfmx_clean* cl) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  for (DevBuf* b : {&cl->work, &cl->in_v, &cl->in_n, &cl->in_f, &cl->out_v, &cl->out_n, &cl->out_f, &cl->vsrc, &cl->fsrc}) b->release();
+  cl->work.release();
+  cl->in.release();
+  cl->out.release();
   cl->t.destroy();
   delete cl;
 }
@@ -310,18 +261,9 @@ int sfmx_clean_run(sfmx_ctx* ctx, sfmx_clean* cl, const double* verts, const dou
   SFMX_REQUIRE(ctx, n >= 0 && m >= 0 && n < (1 << 30) && m < (1 << 30) && (n == 0 || verts) && (m == 0 || faces));
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   if (on_device) return cl_run(ctx, cl, verts, normals, n, faces, m, p, n_verts_out, n_faces_out, n_components, largest);
-  hipStream_t s = ctx->stream;
-  const size_t vb = (size_t)n * 24, fb = (size_t)m * 12;
-  SFMX_HIP(ctx, cl->in_v.ensure(vb));
-  SFMX_HIP(ctx, cl->in_f.ensure(fb));
-  if (n > 0) SFMX_HIP(ctx, hipMemcpyAsync(cl->in_v.p, verts, vb, hipMemcpyHostToDevice, s));
-  if (m > 0) SFMX_HIP(ctx, hipMemcpyAsync(cl->in_f.p, faces, fb, hipMemcpyHostToDevice, s));
-  if (normals) {
-    SFMX_HIP(ctx, cl->in_n.ensure(vb));
-    if (n > 0) SFMX_HIP(ctx, hipMemcpyAsync(cl->in_n.p, normals, vb, hipMemcpyHostToDevice, s));
-  }
-  return cl_run(ctx, cl, cl->in_v.as<double>(), normals ? cl->in_n.as<double>() : nullptr, n, cl->in_f.as<int32_t>(), m, p, n_verts_out,
-                n_faces_out, n_components, largest);
+  MeshDev d;
+  SFMX_HIP(ctx, cl->in.stage(verts, normals, n, faces, m, ctx->stream, d));
+  return cl_run(ctx, cl, d.verts, d.normals, n, d.faces, m, p, n_verts_out, n_faces_out, n_components, largest);
 }
 
 int sfmx_clean_fusion(sfmx_ctx* ctx, sfmx_clean* cl, const sfmx_fusion* fu, const sfmx_clean_params* p, int* n_verts_out,
@@ -344,12 +286,8 @@ int sfmx_clean_read(sfmx_ctx* ctx, sfmx_clean* cl, double* verts_out, double* no
   SFMX_REQUIRE(ctx, ctx && cl && cl->done);
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const size_t nv = (size_t)cl->nv_out, nf = (size_t)cl->nf_out, n = (size_t)cl->n;
-  if (verts_out && nv) SFMX_HIP(ctx, hipMemcpyAsync(verts_out, cl->out_v.p, nv * 24, hipMemcpyDeviceToHost, s));
-  if (normals_out && nv && cl->has_normals) SFMX_HIP(ctx, hipMemcpyAsync(normals_out, cl->out_n.p, nv * 24, hipMemcpyDeviceToHost, s));
-  if (faces_out && nf) SFMX_HIP(ctx, hipMemcpyAsync(faces_out, cl->out_f.p, nf * 12, hipMemcpyDeviceToHost, s));
-  if (vert_src && nv) SFMX_HIP(ctx, hipMemcpyAsync(vert_src, cl->vsrc.p, nv * 4, hipMemcpyDeviceToHost, s));
-  if (face_src && nf) SFMX_HIP(ctx, hipMemcpyAsync(face_src, cl->fsrc.p, nf * 4, hipMemcpyDeviceToHost, s));
+  const size_t n = (size_t)cl->n;
+  SFMX_HIP(ctx, cl->out.read(verts_out, normals_out, faces_out, vert_src, face_src, s));
   if (vert_label && n) SFMX_HIP(ctx, hipMemcpyAsync(vert_label, cl->lab, n * 4, hipMemcpyDeviceToHost, s));
   if (vert_comp_faces && n) SFMX_HIP(ctx, hipMemcpyAsync(vert_comp_faces, cl->vcf, n * 4, hipMemcpyDeviceToHost, s));
   SFMX_HIP(ctx, hipStreamSynchronize(s));
@@ -361,18 +299,13 @@ int sfmx_clean_sizes(const sfmx_clean* cl, int* n, int* m, int* n_verts_out, int
   if (!cl || !cl->done) return SFMX_ERR_INVALID;
   if (n) *n = cl->n;
   if (m) *m = cl->m;
-  if (n_verts_out) *n_verts_out = cl->nv_out;
-  if (n_faces_out) *n_faces_out = cl->nf_out;
+  if (n_verts_out) *n_verts_out = cl->out.nv_out;
+  if (n_faces_out) *n_faces_out = cl->out.nf_out;
   return SFMX_OK;
 }
 
 int sfmx_clean_device_surface(const sfmx_clean* cl, const double** verts, const double** normals) {
-  if (verts) *verts = nullptr;
-  if (normals) *normals = nullptr;
-  if (!cl || !cl->done) return -1;
-  if (verts) *verts = cl->out_v.as<double>();
-  if (normals && cl->has_normals) *normals = cl->out_n.as<double>();
-  return cl->nv_out;
+  return MeshCompact::device_surface(cl && cl->done ? &cl->out : nullptr, verts, normals);
 }
 
 double sfmx_clean_last_us(const sfmx_clean* cl) { return cl ? cl->t.us : 0.0; }
@@ -380,12 +313,5 @@ double sfmx_clean_last_us(const sfmx_clean* cl) { return cl ? cl->t.us : 0.0; }
 }  // extern "C"
 
 int sfmx_clean_device_mesh(const sfmx_clean* cl, const double** verts, const int32_t** faces, int* n_faces) {
-  *verts = nullptr;
-  *faces = nullptr;
-  *n_faces = 0;
-  if (!cl || !cl->done) return -1;
-  *verts = cl->out_v.as<double>();
-  *faces = cl->out_f.as<int32_t>();
-  *n_faces = cl->nf_out;
-  return cl->nv_out;
+  return MeshCompact::device_mesh(cl && cl->done ? &cl->out : nullptr, verts, faces, nullptr, n_faces);
 }

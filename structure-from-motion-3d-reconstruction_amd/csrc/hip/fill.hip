@@ -86,7 +86,8 @@ __global__ __launch_bounds__(256) void k_fl_gaps(const unsigned long long* __res
       c[2]++;
     }
   }
-  et_block_sums<3>(c, counters + FL_EDGE_PART);
+  const int s = sfmx_block_sums(c);
+  if (threadIdx.x < 3) counters[FL_EDGE_PART + 3 * blockIdx.x + threadIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void k_fl_class(int n, const int* __restrict__ outc, const int* __restrict__ inc,
@@ -98,7 +99,8 @@ __global__ __launch_bounds__(256) void k_fl_class(int n, const int* __restrict__
     next[v] = -1;
     c[0] += (o != 0 || i != 0) ? 1 : 0;
   }
-  et_block_sums<1>(c, counters + FL_CPLX_PART);
+  const int s = sfmx_block_sums(c);
+  if (threadIdx.x == 0) counters[FL_CPLX_PART + blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void k_fl_walk(int n, const int* __restrict__ next, int max_edges, int* __restrict__ kv, int* __restrict__ kf,
@@ -122,7 +124,8 @@ __global__ __launch_bounds__(256) void k_fl_walk(int n, const int* __restrict__ 
     kf[v] = L == 3 ? 1 : L;
     c[0] += L > 0 ? 1 : 0;
   }
-  et_block_sums<1>(c, counters + FL_LOOP_PART);
+  const int s = sfmx_block_sums(c);
+  if (threadIdx.x == 0) counters[FL_LOOP_PART + blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void k_fl_emit(const double* __restrict__ verts, const double* __restrict__ normals, int n, int m,
@@ -180,7 +183,7 @@ struct sfmx_fill {
   // work: the gap counts, next, the irregular bytes, the loop counts, their scans, the scan's partials and the counters.
   // table: the keys and the two use counters of every slot.
   DevBuf work, table;
-  DevBuf in_v, in_n, in_f;  // host inputs, staged
+  MeshInput in;  // host inputs, staged
   DevBuf out_v, out_n, out_f;
   bool done = false, has_normals = false;
   int n = 0, m = 0, n_out = 0, m_out = 0, counts[8] = {};
@@ -339,7 +342,8 @@ void sfmx_fill_destroy(sfmx_ctx* ctx, sfmx_fill* fl) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  for (DevBuf* b : {&fl->work, &fl->table, &fl->in_v, &fl->in_n, &fl->in_f, &fl->out_v, &fl->out_n, &fl->out_f}) b->release();
+  fl->in.release();
+  for (DevBuf* b : {&fl->work, &fl->table, &fl->out_v, &fl->out_n, &fl->out_f}) b->release();
   fl->t.destroy();
   delete fl;
 }
@@ -351,16 +355,11 @@ int sfmx_fill_run(sfmx_ctx* ctx, sfmx_fill* fl, const double* verts, const doubl
   SFMX_REQUIRE(ctx, sfmx_fill_check_params(p) == SFMX_OK);
   SFMX_REQUIRE(ctx, n >= 0 && m >= 0 && n < (1 << 24) && m < (1 << 30) && (n == 0 || verts) && (m == 0 || faces));
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
-  if (on_device) return fl_run(ctx, fl, verts, n > 0 ? normals : nullptr, n, faces, m, p);
-  hipStream_t s = ctx->stream;
-  const size_t vb = (size_t)n * 24, fb = (size_t)m * 12;
-  SFMX_HIP(ctx, fl->in_v.ensure(vb));
-  SFMX_HIP(ctx, fl->in_f.ensure(fb));
-  if (normals) SFMX_HIP(ctx, fl->in_n.ensure(vb));
-  if (n > 0) SFMX_HIP(ctx, hipMemcpyAsync(fl->in_v.p, verts, vb, hipMemcpyHostToDevice, s));
-  if (n > 0 && normals) SFMX_HIP(ctx, hipMemcpyAsync(fl->in_n.p, normals, vb, hipMemcpyHostToDevice, s));
-  if (m > 0) SFMX_HIP(ctx, hipMemcpyAsync(fl->in_f.p, faces, fb, hipMemcpyHostToDevice, s));
-  return fl_run(ctx, fl, fl->in_v.as<double>(), normals && n > 0 ? fl->in_n.as<double>() : nullptr, n, fl->in_f.as<int32_t>(), m, p);
+  const double* nrm = n > 0 ? normals : nullptr;  // an empty mesh passes no normals on, from the host or from the device
+  if (on_device) return fl_run(ctx, fl, verts, nrm, n, faces, m, p);
+  MeshDev d;
+  SFMX_HIP(ctx, fl->in.stage(verts, nrm, n, faces, m, ctx->stream, d));
+  return fl_run(ctx, fl, d.verts, d.normals, n, d.faces, m, p);
 }
 
 int sfmx_fill_fusion(sfmx_ctx* ctx, sfmx_fill* fl, const sfmx_fusion* fu, const sfmx_fill_params* p) {

@@ -22,7 +22,7 @@
 //   k_lv_deg      per slot of the edge table: the degrees of both ends;  k_scan_*: the rows;  k_lv_fill: the rows' neighbours
 //   k_lv_sweep    T launches: one thread per node gathers its row from one buffer and writes the other
 //   k_lv_corners  per corner: corner_adj and corner_sample
-//   k_lv_bake     k_tx_bake's block shape with three more int32 per half cell in LDS: the levelled atlas
+//   k_lv_bake     k_tx_bake's body (sfmx_texture_dev.h: tx_bake<true>) with three more int32 per half cell in LDS: the levelled atlas
 // Two host synchronisations per run: after the node count, and at the end (the counts).
 #include <cmath>
 
@@ -33,8 +33,6 @@
 namespace {
 
 constexpr int LV_ITER_MAX = 65536;
-constexpr int LV_GROUP = 16;  // cells per block of k_lv_bake, as k_tx_bake
-constexpr int LV_REC = 26;    // eight-byte words per half cell in LDS, as k_tx_bake
 
 enum { LV_FLAG = 0, LV_NODES, LV_SEAM, LV_PINNED, LV_EDGES, LV_NWORDS = 8 };  // int32 words read back
 
@@ -50,30 +48,6 @@ __device__ __forceinline__ void lv_count(bool pred, int* counter) {
   if (b && (int)(threadIdx.x & 63) == __ffsll((long long)b) - 1) atomicAdd(counter, __popcll(b));
 }
 
-// DESIGN.md 25's bilinear g (not rounded) of view S at the point X; false where the texel would be `fill`
-__device__ __forceinline__ bool lv_g(const RsCam& cam, long long off, const uint8_t* __restrict__ img, double X0, double X1, double X2,
-                                     double& g) {
-  const double* R = cam.R;
-  const double p0 = X0 - cam.c[0], p1 = X1 - cam.c[1], p2 = X2 - cam.c[2];
-  const double q0 = (R[0] * p0 + R[1] * p1) + R[2] * p2;
-  const double q1 = (R[3] * p0 + R[4] * p1) + R[5] * p2;
-  const double q2 = (R[6] * p0 + R[7] * p1) + R[8] * p2;
-  const double u = (cam.f * q0) / q2 + cam.cx, v = (cam.f * q1) / q2 + cam.cy;
-  if (!(q2 > 0.0 && isfinite(u) && isfinite(v))) return false;
-  const int w = cam.w, h = cam.h;
-  const double uc = fmin(fmax(u, -1.0), (double)w), vc = fmin(fmax(v, -1.0), (double)h);
-  const double x0 = floor(uc), y0 = floor(vc);
-  const double ax = uc - x0, ay = vc - y0;
-  const int xi0 = min(max((int)x0, 0), w - 1), xi1 = min(max((int)x0 + 1, 0), w - 1);
-  const int yi0 = min(max((int)y0, 0), h - 1), yi1 = min(max((int)y0 + 1, 0), h - 1);
-  const uint8_t* I0 = img + off + (long long)yi0 * w;
-  const uint8_t* I1 = img + off + (long long)yi1 * w;
-  const double top = (1.0 - ax) * (double)I0[xi0] + ax * (double)I0[xi1];
-  const double bot = (1.0 - ax) * (double)I1[xi0] + ax * (double)I1[xi1];
-  g = (1.0 - ay) * top + ay * bot;
-  return true;
-}
-
 __global__ __launch_bounds__(256) void k_lv_insert(const double* __restrict__ verts, const int* __restrict__ faces, long long corners,
                                                    int n, const int* __restrict__ fview, const RsSlot* __restrict__ slots,
                                                    const uint8_t* __restrict__ img, int L, int fill, unsigned long long* keys,
@@ -86,8 +60,8 @@ __global__ __launch_bounds__(256) void k_lv_insert(const double* __restrict__ ve
   if (t < corners) {
     const long long f = t / 3;
     const int c = (int)(t - 3 * f);
-    const int a0 = faces[3 * f], a1 = faces[3 * f + 1], a2 = faces[3 * f + 2];
-    const bool ok = (unsigned)a0 < (unsigned)n && (unsigned)a1 < (unsigned)n && (unsigned)a2 < (unsigned)n;
+    int a0, a1, a2;
+    const bool ok = mesh_face(faces, (int)f, n, a0, a1, a2);
     if (!ok && c == 0) atomicOr(&words[LV_FLAG], 1);  // the call fails; nothing is read through the index
     const int k = fview[f];
     if (ok && k >= 0) {
@@ -122,9 +96,9 @@ __global__ __launch_bounds__(256) void k_lv_insert(const double* __restrict__ ve
   const RsSlot& S = slots[k];
   const double dl = (double)L;
   const double X0 = (dl * verts[3 * (size_t)v]) / dl, X1 = (dl * verts[3 * (size_t)v + 1]) / dl, X2 = (dl * verts[3 * (size_t)v + 2]) / dl;
-  double g;
   int fx = 256 * fill;
-  if (lv_g(S.cam, S.img_off, img, X0, X1, X2, g)) fx = (int)(long long)floor(g * 256.0 + 0.5);
+  const TxSample sm = tx_sample(S.cam, S.img_off, img, X0, X1, X2);
+  if (sm.ok) fx = (int)(long long)floor(sm.g * 256.0 + 0.5);
   ids[slot] = id;
   nkey[id] = key;
   nfx[id] = fx;
@@ -225,95 +199,13 @@ __global__ __launch_bounds__(256) void k_lv_bake(const double* __restrict__ vert
                                                  const int* __restrict__ list, const int* __restrict__ fview,
                                                  const int* __restrict__ cadj, const RsSlot* __restrict__ slots,
                                                  const uint8_t* __restrict__ img, TxLayout lay, uint8_t* __restrict__ atlas) {
-  __shared__ double rec[2 * LV_GROUP][LV_REC];  // X a, b, c (9), the camera (16 words), the image's offset
-  __shared__ int idx[2 * LV_GROUP][4];          // the face's corners and its view, -1: a half without a face
-  __shared__ int adj[2 * LV_GROUP][4];          // the corners' offsets
-  const int S = lay.S, L = S - 2, row = blockIdx.x, g0 = blockIdx.y * LV_GROUP;
-  const int gc = min(LV_GROUP, lay.C - g0);  // cells of this group
-  if (threadIdx.x < 2 * LV_GROUP) {
-    const int hl = threadIdx.x, c = row * lay.C + g0 + (hl >> 1);
-    const long long r = 2ll * c + (hl & 1);
-    int v = -1, a = 0, b = 0, cc = 0, ga = 0, gb = 0, gcc = 0;
-    if ((hl >> 1) < gc && c < lay.cells && c != lay.fill_cell && r < lay.n_tex) {
-      const int f = list[r];
-      v = fview[f];
-      a = faces[3 * (size_t)f];  // the call's range check has passed
-      b = faces[3 * (size_t)f + 1];
-      cc = faces[3 * (size_t)f + 2];
-      ga = cadj[3 * (size_t)f];
-      gb = cadj[3 * (size_t)f + 1];
-      gcc = cadj[3 * (size_t)f + 2];
-    }
-    idx[hl][0] = a;
-    idx[hl][1] = b;
-    idx[hl][2] = cc;
-    idx[hl][3] = v;
-    adj[hl][0] = ga;
-    adj[hl][1] = gb;
-    adj[hl][2] = gcc;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 2 * LV_GROUP * LV_REC; e += 256) {
-    const int hl = e / LV_REC, j = e % LV_REC, v = idx[hl][3];
-    if (v < 0) continue;
-    unsigned long long x;  // bits: the camera's last word is its two ints
-    if (j < 9) {
-      x = reinterpret_cast<const unsigned long long*>(verts)[3 * (size_t)idx[hl][j / 3] + (j % 3)];
-    } else {
-      const unsigned long long* s = reinterpret_cast<const unsigned long long*>(slots + v);  // words 0 .. 15 the camera, 16 key_off, 17 img_off
-      x = s[j == LV_REC - 1 ? 17 : j - 9];
-    }
-    reinterpret_cast<unsigned long long*>(rec[hl])[j] = x;
-  }
-  __syncthreads();
-  const int rw = gc * (S + 1), total = rw * S;
-  const size_t base = (size_t)row * S * lay.W + (size_t)g0 * (S + 1);
-  for (int t = threadIdx.x; t < total; t += 256) {
-    const int ly = t / rw, x = t - ly * rw;
-    const int cb = x / (S + 1), lx = x - cb * (S + 1);
-    const int half = lx + ly >= S ? 1 : 0;
-    const int i = half ? S - lx : lx, j = half ? S - 1 - ly : ly;
-    const int hl = 2 * cb + half;
-    int out = lay.fill;
-    if (idx[hl][3] >= 0) {
-      const double* r = rec[hl];
-      const int i2 = min(i, L), j2 = min(j, L - i2);
-      const double wa = (double)(L - i2 - j2), wb = (double)i2, wc = (double)j2, dl = (double)L;
-      const double X0 = ((wa * r[0] + wb * r[3]) + wc * r[6]) / dl;
-      const double X1 = ((wa * r[1] + wb * r[4]) + wc * r[7]) / dl;
-      const double X2 = ((wa * r[2] + wb * r[5]) + wc * r[8]) / dl;
-      const double* R = r + 9;  // R[0 .. 8], c = R[9 .. 11], f, cx, cy = R[12 .. 14]
-      const double p0 = X0 - R[9], p1 = X1 - R[10], p2 = X2 - R[11];
-      const double q0 = (R[0] * p0 + R[1] * p1) + R[2] * p2;
-      const double q1 = (R[3] * p0 + R[4] * p1) + R[5] * p2;
-      const double q2 = (R[6] * p0 + R[7] * p1) + R[8] * p2;
-      const double u = (R[12] * q0) / q2 + R[13], v = (R[12] * q1) / q2 + R[14];
-      if (q2 > 0.0 && isfinite(u) && isfinite(v)) {
-        const int2 wh = *reinterpret_cast<const int2*>(r + 24);
-        const long long off = *reinterpret_cast<const long long*>(r + 25);
-        const int w = wh.x, h = wh.y;
-        const double uc = fmin(fmax(u, -1.0), (double)w), vc = fmin(fmax(v, -1.0), (double)h);
-        const double x0 = floor(uc), y0 = floor(vc);
-        const double ax = uc - x0, ay = vc - y0;
-        const int xi0 = min(max((int)x0, 0), w - 1), xi1 = min(max((int)x0 + 1, 0), w - 1);
-        const int yi0 = min(max((int)y0, 0), h - 1), yi1 = min(max((int)y0 + 1, 0), h - 1);
-        const uint8_t* I0 = img + off + (long long)yi0 * w;
-        const uint8_t* I1 = img + off + (long long)yi1 * w;
-        const double top = (1.0 - ax) * (double)I0[xi0] + ax * (double)I0[xi1];
-        const double bot = (1.0 - ax) * (double)I1[xi0] + ax * (double)I1[xi1];
-        const double g = (1.0 - ay) * top + ay * bot;
-        const long long N = ((long long)(L - i2 - j2) * adj[hl][0] + (long long)i2 * adj[hl][1]) + (long long)j2 * adj[hl][2];
-        out = (int)fmin(255.0, fmax(0.0, floor((g + (double)N / (double)(256 * L)) + 0.5)));
-      }
-    }
-    atlas[base + (size_t)ly * lay.W + x] = (uint8_t)out;
-  }
+  tx_bake<true>(verts, faces, list, fview, cadj, slots, img, lay, atlas);
 }
 
 }  // namespace
 
 struct sfmx_level {
-  DevBuf in_v, in_f;                  // host inputs, staged
+  MeshInput in;                       // host inputs, staged
   DevBuf nkeys, ids;                  // the node table: keys and node numbers per slot
   DevBuf cslot, cnode;                // per corner: its node's slot, its node
   DevBuf nkey, nfx, g0, g1, pin;      // per node
@@ -342,8 +234,8 @@ int lv_run(sfmx_ctx* ctx, sfmx_level* lv, const sfmx_texture* tx, const double* 
   const size_t eslots = et_slots(mm);         // at most 3 m node edges in at least 4 m slots
   const unsigned nbc = (unsigned)((corners + 255) / 256), nbv = (unsigned)((nn + 255) / 256), nbf = (unsigned)((mm + 255) / 256);
   const int* fview = tx->fview.as<int>();
-  const RsSlot* slots = tx->d_slots.as<RsSlot>();
-  const uint8_t* img = tx->img.as<uint8_t>();
+  const RsSlot* slots = tx->vs.d_slots.as<RsSlot>();
+  const uint8_t* img = tx->vs.img.as<uint8_t>();
 
   SFMX_HIP(ctx, lv->res.ensure(LV_NWORDS * 4));
   SFMX_HIP(ctx, lv->vviews.ensure(nn * 4));
@@ -420,8 +312,8 @@ int lv_run(sfmx_ctx* ctx, sfmx_level* lv, const sfmx_texture* tx, const double* 
   if (lay.cells > 0) {
     const int rows = lay.H / lay.S;
     SFMX_HIP(ctx, lv->tb.begin(ctx));
-    k_lv_bake<<<dim3((unsigned)rows, (unsigned)((lay.C + LV_GROUP - 1) / LV_GROUP)), 256, 0, s>>>(
-        verts, faces, tx_face_list(tx), fview, lv->cadj.as<int>(), slots, img, lay, lv->atlas.as<uint8_t>());
+    k_lv_bake<<<dim3((unsigned)rows, (unsigned)((lay.C + TX_GROUP - 1) / TX_GROUP)), 256, 0, s>>>(
+        verts, faces, tx->list, fview, lv->cadj.as<int>(), slots, img, lay, lv->atlas.as<uint8_t>());
     SFMX_HIP(ctx, lv->tb.end(ctx));
   }
   SFMX_HIP(ctx, hipGetLastError());
@@ -482,7 +374,8 @@ void sfmx_level_destroy(sfmx_ctx* ctx, sfmx_level* lv) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  for (DevBuf* b : {&lv->in_v, &lv->in_f, &lv->nkeys, &lv->ids, &lv->cslot, &lv->cnode, &lv->nkey, &lv->nfx, &lv->g0, &lv->g1, &lv->pin, &lv->deg,
+  lv->in.release();
+  for (DevBuf* b : {&lv->nkeys, &lv->ids, &lv->cslot, &lv->cnode, &lv->nkey, &lv->nfx, &lv->g0, &lv->g1, &lv->pin, &lv->deg,
                     &lv->row, &lv->cur, &lv->adj, &lv->aux, &lv->ekeys, &lv->euses, &lv->vsum, &lv->res, &lv->vviews, &lv->cadj, &lv->csamp,
                     &lv->atlas})
     b->release();
@@ -506,13 +399,9 @@ int sfmx_level_run(sfmx_ctx* ctx, sfmx_level* lv, const sfmx_texture* tx, const 
   SFMX_REQUIRE(ctx, (verts || n == 0) && (faces || m == 0));
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   if (on_device) return lv_run(ctx, lv, tx, verts, n, faces, m, p->iterations);
-  hipStream_t s = ctx->stream;
-  const size_t vbytes = (size_t)n * 24, fbytes = (size_t)m * 12;
-  SFMX_HIP(ctx, lv->in_v.ensure(vbytes));
-  SFMX_HIP(ctx, lv->in_f.ensure(fbytes));
-  if (n > 0) SFMX_HIP(ctx, hipMemcpyAsync(lv->in_v.p, verts, vbytes, hipMemcpyHostToDevice, s));
-  if (m > 0) SFMX_HIP(ctx, hipMemcpyAsync(lv->in_f.p, faces, fbytes, hipMemcpyHostToDevice, s));
-  return lv_run(ctx, lv, tx, lv->in_v.as<double>(), n, lv->in_f.as<int32_t>(), m, p->iterations);
+  MeshDev d;
+  SFMX_HIP(ctx, lv->in.stage(verts, nullptr, n, faces, m, ctx->stream, d));
+  return lv_run(ctx, lv, tx, d.verts, n, d.faces, m, p->iterations);
 }
 
 int sfmx_level_read(sfmx_ctx* ctx, sfmx_level* lv, uint8_t* atlas, int32_t* corner_adj, int32_t* corner_sample, int32_t* vertex_views) {

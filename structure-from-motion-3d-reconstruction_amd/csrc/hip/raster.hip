@@ -27,7 +27,7 @@
 //   k_rs_sum      one block adds the partial counts
 //   k_rs_resolve  one thread per pixel, a wave is an 8 x 8 tile (as k_rc_render): the winner's edge functions, depth, point,
 //                 normal, shade and grey; hits and back_pixels are a ballot and one atomicAdd per wave each
-// The first three kernels and the device helpers live in sfmx_raster_dev.h, which visib.hip shares; this file uses their
+// The first three kernels and the device helpers live in sfmx_raster_dev.h, which visib.hip and texture.hip share; this file uses their
 // one-camera form (BATCH = false).
 #include <cmath>
 
@@ -44,7 +44,8 @@ __global__ __launch_bounds__(256) void k_rs_sum(const unsigned long long* __rest
 #pragma unroll
     for (int k = 0; k < RS_NPART; k++) cnt[k] += parts[(size_t)b * RS_NPART + k];
   }
-  rs_block_sums(cnt, totals);
+  const unsigned long long sum = sfmx_block_sums(cnt);
+  if (threadIdx.x < RS_NPART) totals[threadIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(256) void k_rs_resolve(const unsigned long long* __restrict__ keys, const int* __restrict__ faces,

@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "sfmx_mesh_dev.h"
+
 constexpr unsigned long long ET_EMPTY = ~0ull;
 
 __device__ __forceinline__ unsigned long long et_hash(unsigned long long k) {
@@ -54,8 +56,8 @@ __device__ __forceinline__ void et_insert(int a, int b, unsigned long long* keys
 // fails) and is skipped, so that nothing is accessed through the index
 __device__ __forceinline__ void et_insert_face(const int* __restrict__ faces, int f, int n, unsigned long long* keys, int* uses,
                                                unsigned long long mask, int nbits, int* __restrict__ flag) {
-  const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  if ((unsigned)a >= (unsigned)n || (unsigned)b >= (unsigned)n || (unsigned)c >= (unsigned)n) {
+  int a, b, c;
+  if (!mesh_face(faces, f, n, a, b, c)) {
     *flag = 1;
     return;
   }
@@ -74,20 +76,4 @@ static inline int et_nbits(int n) {
   int nbits = 1;
   while ((1ll << nbits) < n) nbits++;
   return nbits;
-}
-
-// sums of K ints over a block of 256 into part[K * blockIdx.x ..]
-template <int K>
-__device__ __forceinline__ void et_block_sums(int (&x)[K], int* __restrict__ part) {
-  __shared__ int red[4][K];
-#pragma unroll
-  for (int k = 0; k < K; k++)
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) x[k] += __shfl_xor(x[k], s, 64);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < K; k++) red[threadIdx.x >> 6][k] = x[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < K) part[K * blockIdx.x + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }

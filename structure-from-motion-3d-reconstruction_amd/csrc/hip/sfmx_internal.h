@@ -251,3 +251,23 @@ struct StageTimer {
 size_t sfmx_scan_aux(int n);
 void sfmx_scan(const int* in, bool popc, int n, int* out, int* aux, hipStream_t s);
 void sfmx_scan_total(const int* in, bool popc, const int* out, int n, int* total, hipStream_t s);
+
+// The sums of K integers over a block of 256 threads: thread j < K returns the block's sum of v[j] (the other threads that of
+// v[0]).  Every thread of the block calls it; a kernel that calls it twice puts a __syncthreads() between the calls, since both
+// use the same LDS.
+template <class T, int K> __device__ __forceinline__ T sfmx_block_sums(T (&v)[K]) {
+  __shared__ T sh[4][K];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; k++) sh[wave][k] = v[k];
+  }
+  __syncthreads();
+  const int j = threadIdx.x < K ? threadIdx.x : 0;
+  return (sh[0][j] + sh[1][j]) + (sh[2][j] + sh[3][j]);
+}

@@ -1,22 +1,33 @@
 // sfmx_raster_dev.h - the exact z-buffer as the device kernels build it: the camera, the projected vertex, the
 // oriented edge functions of a face, the key of a fragment and its contest, and the three kernels that turn a mesh into a key
-// image (project, faces, big).  Shared by raster.hip (one camera per run, with the face counts) and visib.hip (a batch of
-// cameras per launch, the view being the grid's second dimension, without the counts), so that both evaluate the same
-// expressions in the same order: visibility compares a vertex with the key image the renderer would have made.
+// image (project, faces, big).  Shared by raster.hip (one camera per run, with the face counts) and, through RsViewSet, by
+// visib.hip, texture.hip and level.hip (a batch of cameras per launch, the view being the grid's second dimension, without the
+// counts), so that all evaluate the same expressions in the same order: visibility and texturing compare a vertex with the key
+// image the renderer would have made, through the one test rs_vertex_sees.
 //
 // BATCH = false is the renderer's form: the camera by value, one set of buffers.  BATCH = true reads view blockIdx.y's camera and
 // the place of its key image from slots[] (a wave-uniform index, so through the scalar cache) and finds its projected vertices,
 // flags, list of big faces and counters at view * n, view * n, view * m and view * RS_NWORDS.
+//
+// RsViewSet is the multi-view z-buffer as one object: the ordered list of cameras with an optional u8 image each, the batches
+// of a run and the launch group that builds one batch's key images.
 #pragma once
 #include <cmath>
+#include <vector>
 
 #include "sfmx_internal.h"
+#include "sfmx_mesh_dev.h"
 
 namespace {
 
 // k_rs_faces<BATCH, SMALL>: a box of at most SMALL pixel centres is walked by the face's own thread; each user states its own
 constexpr int RS_FACE_BLOCKS = 1024;  // blocks of k_rs_faces at most (per view)
 constexpr int RS_BIG_BLOCKS = 512;    // blocks of k_rs_big (the renderer's; a batch uses fewer per view)
+// a batch of views (RsViewSet); they change the speed only
+constexpr size_t RS_BATCH_BUDGET = (size_t)256 << 20;  // bytes a batch's key slab, per-(view, vertex) records and big-face lists may take
+constexpr int RS_MAX_BATCH = 64;                       // one bit per view in a vertex's mask
+constexpr int RS_BATCH_BIG_BLOCKS = 64;                // blocks of k_rs_big per view
+constexpr int RS_BATCH_SMALL = 64;                     // as raster.hip's RS_SMALL: a larger box of pixel centres goes to k_rs_big
 
 enum { RS_BEHIND = 0, RS_OUTSIDE, RS_DEGENERATE, RS_BACK, RS_CULLED, RS_DRAWN, RS_BIG, RS_FRAGMENTS, RS_NPART };
 // device counters: four uint32 (below), then (the renderer only) the RS_NPART uint64 totals
@@ -127,21 +138,33 @@ __device__ __forceinline__ double rs_depth(const RsCam& cam, double X0, double X
   return (cam.R[6] * p0 + cam.R[7] * p1) + cam.R[8] * p2;
 }
 
-// the block's sums of v[] into out[0 .. RS_NPART)
-__device__ __forceinline__ void rs_block_sums(unsigned long long (&v)[RS_NPART], unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long sh[4][RS_NPART];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < RS_NPART; k++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+// What view S of a batch sees of vertex i (X0, X1, X2), whose projection and flags lie at `at` = view * n + i: the vertex is off
+// the image (not inband, or its snapped pixel outside), occluded (deeper than the key there by more than depth_tol) or visible;
+// then px is its pixel and p = X - c.  One double addition and one comparison against the key.
+enum { RS_SEES_OFF = 0, RS_SEES_OCCLUDED, RS_SEES_VISIBLE };
+struct RsSight {
+  int state;
+  long long px;
+  double p0, p1, p2;
+};
+__device__ __forceinline__ RsSight rs_vertex_sees(const RsSlot& S, const RsVert* __restrict__ pv, const uint8_t* __restrict__ fl,
+                                                  const unsigned long long* __restrict__ keys, size_t at, double X0, double X1,
+                                                  double X2, double depth_tol) {
+  RsSight r{RS_SEES_OFF, 0, 0.0, 0.0, 0.0};
+  if (!(fl[at] & 2u)) return r;  // not inband
+  const RsVert P = pv[at];
+  const int x = (P.U + 128) >> 8, y = (P.V + 128) >> 8;
+  if (x < 0 || x >= S.cam.w || y < 0 || y >= S.cam.h) return r;
+  r.px = (long long)y * S.cam.w + x;
+  const unsigned long long key = keys[S.key_off + r.px];
+  const double q2 = rs_depth(S.cam, X0, X1, X2, r.p0, r.p1, r.p2);
+  bool visible = true;
+  if (key != ~0ull) {
+    const double D = (double)__uint_as_float((unsigned)(key >> 32));
+    visible = q2 <= D + depth_tol;  // false for a NaN
   }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < RS_NPART; k++) sh[wave][k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < RS_NPART) out[threadIdx.x] = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+  r.state = visible ? RS_SEES_VISIBLE : RS_SEES_OCCLUDED;
+  return r;
 }
 
 template <bool BATCH>
@@ -195,8 +218,8 @@ __global__ __launch_bounds__(256) void k_rs_faces(const int* __restrict__ faces,
     const int f = base + threadIdx.x;
     bool is_big = false;
     if (f < m) {
-      const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-      if ((unsigned)a >= (unsigned)n || (unsigned)b >= (unsigned)n || (unsigned)c >= (unsigned)n) {
+      int a, b, c;
+      if (!mesh_face(faces, f, n, a, b, c)) {
         atomicOr(&counters[RS_FLAG], 1u);  // the call fails; nothing is read through the index
       } else {
         const unsigned fa = fl[a], fb = fl[b], fc = fl[c], all = fa & fb & fc;
@@ -261,7 +284,10 @@ __global__ __launch_bounds__(256) void k_rs_faces(const int* __restrict__ faces,
       if (is_big) big[at + __popcll(bm & ((1ull << lane) - 1ull))] = f;
     }
   }
-  if (!BATCH) rs_block_sums(cnt, parts + (size_t)blockIdx.x * RS_NPART);
+  if (!BATCH) {
+    const unsigned long long sum = sfmx_block_sums(cnt);
+    if (threadIdx.x < RS_NPART) parts[(size_t)blockIdx.x * RS_NPART + threadIdx.x] = sum;
+  }
 }
 
 template <bool BATCH>
@@ -322,7 +348,150 @@ __global__ __launch_bounds__(256) void k_rs_big(const int* __restrict__ faces, i
     __syncthreads();
     if (threadIdx.x == 0 && drawn) cnt[RS_DRAWN]++;
   }
-  if (!BATCH) rs_block_sums(cnt, parts + (size_t)blockIdx.x * RS_NPART);
+  if (!BATCH) {
+    const unsigned long long sum = sfmx_block_sums(cnt);
+    if (threadIdx.x < RS_NPART) parts[(size_t)blockIdx.x * RS_NPART + threadIdx.x] = sum;
+  }
 }
+
+// views [first, first + count) of a view set, and the pixels of their key images
+struct RsBatch {
+  int first, count;
+  size_t px;
+};
+
+// An ordered list of cameras, each with or without a u8 image in one slab on the device, and the exact z-buffers of a mesh for
+// them, a batch at a time.  A batch is sized so that its key images, projected vertices (16 + 1 bytes per view and vertex) and
+// lists of big faces stay within RS_BATCH_BUDGET, unless set_batch forces its size.  Which views need an image is the owner's rule.
+struct RsViewSet {
+  std::vector<sfmx_fusion_view> views;
+  std::vector<long long> img_off;  // of a view's image in the image slab, -1 without one
+  std::vector<RsSlot> slots;       // of the last prepare, as uploaded
+  std::vector<RsBatch> batches;    // of the last plan
+  long long img_used = 0;
+  int forced_batch = 0, last_batch = 0;
+  size_t key_px = 0;  // of the last plan: the most key pixels of a batch
+  int widest = 0;     // and the most views
+  DevBuf img, d_slots;
+  DevBuf keys, pv, fl, big, rcounters;  // one batch's z-buffers
+
+  int reset() {
+    views.clear();
+    img_off.clear();
+    img_used = 0;
+    return SFMX_OK;
+  }
+
+  int add_view(sfmx_ctx* ctx, const sfmx_fusion_view* view, const uint8_t* image, int on_device) {
+    SFMX_REQUIRE(ctx, rs_view_ok(view));
+    long long off = -1;
+    if (image) {
+      SFMX_HIP(ctx, hipSetDevice(ctx->device));
+      const long long px = (long long)view->w * view->h;
+      SFMX_REQUIRE(ctx, img_used + px < (1ll << 40));
+      SFMX_HIP(ctx, sfmx_grow_keep(img, (size_t)img_used, (size_t)(img_used + px), ctx->stream));
+      SFMX_HIP(ctx, hipMemcpyAsync(img.as<uint8_t>() + img_used, image, (size_t)px, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                   ctx->stream));
+      SFMX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller may reuse its buffer
+      off = img_used;
+      img_used += px;
+    }
+    views.push_back(*view);
+    img_off.push_back(off);
+    return SFMX_OK;
+  }
+
+  int add_stereo_view(sfmx_ctx* ctx, const sfmx_fusion_view* view, const sfmx_stereo* st) {
+    SFMX_REQUIRE(ctx, st && view);
+    int w = 0, h = 0;
+    const uint8_t* im = sfmx_stereo_device_rect_left(st, &w, &h);
+    SFMX_REQUIRE(ctx, im && view->w == w && view->h == h);
+    return add_view(ctx, view, im, 1);
+  }
+
+  int view_count() const { return (int)views.size(); }
+
+  int set_batch(int k) {
+    if (k < 0 || k > RS_MAX_BATCH) return SFMX_ERR_INVALID;
+    forced_batch = k;
+    return SFMX_OK;
+  }
+
+  // the batches for a mesh of n vertices and m faces, with key_px and widest
+  void plan(int n, int m) {
+    batches.clear();
+    const int V = (int)views.size();
+    key_px = 0;
+    widest = 0;
+    int k = 0;
+    while (k < V) {
+      size_t bytes = 0, px = 0;
+      int c = 0;
+      while (k + c < V && c < RS_MAX_BATCH) {
+        const size_t p = (size_t)views[k + c].w * (size_t)views[k + c].h;
+        const size_t one = p * 8 + (size_t)n * 17 + (size_t)m * 4;
+        if (forced_batch ? c >= forced_batch : (c > 0 && bytes + one > RS_BATCH_BUDGET)) break;
+        bytes += one;
+        px += p;
+        c++;
+      }
+      batches.push_back({k, c, px});
+      key_px = px > key_px ? px : key_px;
+      widest = c > widest ? c : widest;
+      k += c;
+    }
+  }
+
+  // plans, sizes the z-buffer slabs and uploads the slots of all views: a batch's key images lie back to back in the key slab
+  int prepare(sfmx_ctx* ctx, int n, int m) {
+    plan(n, m);
+    const size_t nn = (size_t)n, mm = (size_t)m, V = views.size();
+    SFMX_HIP(ctx, keys.ensure(key_px * 8));
+    SFMX_HIP(ctx, pv.ensure((size_t)widest * nn * sizeof(RsVert)));
+    SFMX_HIP(ctx, fl.ensure((size_t)widest * nn));
+    SFMX_HIP(ctx, big.ensure((size_t)widest * mm * 4));
+    SFMX_HIP(ctx, rcounters.ensure((size_t)RS_MAX_BATCH * RS_NWORDS * 4));
+    slots.resize(V);
+    for (const RsBatch& b : batches) {
+      long long at = 0;
+      for (int k = b.first; k < b.first + b.count; k++) {
+        slots[k].cam = rs_cam(&views[k]);
+        slots[k].key_off = at;
+        slots[k].img_off = img_off[k] >= 0 ? img_off[k] : 0;
+        at += (long long)views[k].w * views[k].h;
+      }
+    }
+    if (V > 0) {
+      SFMX_HIP(ctx, d_slots.ensure(sizeof(RsSlot) * V));
+      SFMX_HIP(ctx, hipMemcpyAsync(d_slots.p, slots.data(), sizeof(RsSlot) * V, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return SFMX_OK;
+  }
+
+  const RsSlot* batch_slots(const RsBatch& b) const { return d_slots.as<RsSlot>() + b.first; }
+
+  // the key images of batch b for the mesh (n > 0): clear, project, and with faces the two face kernels.  A template, so that
+  // only the files that build z-buffers instantiate the batch kernels (raster.hip and level.hip include this header too).
+  template <int SMALL = RS_BATCH_SMALL> hipError_t zbuffer(const RsBatch& b, const double* verts, int n, const int32_t* faces, int m, double z_min, hipStream_t s) {
+    const unsigned nbv = (unsigned)(((size_t)n + 255) / 256);
+    const int fb = m > (RS_FACE_BLOCKS - 1) * 256 ? RS_FACE_BLOCKS : (m + 255) / 256;
+    const RsSlot* sl = batch_slots(b);
+    hipError_t e = hipMemsetAsync(keys.p, 0xFF, b.px * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(rcounters.p, 0, (size_t)b.count * RS_NWORDS * 4, s);
+    if (e != hipSuccess) return e;
+    k_rs_project<true><<<dim3(nbv, (unsigned)b.count), 256, 0, s>>>(verts, n, RsCam{}, sl, z_min, pv.as<RsVert>(), fl.as<uint8_t>());
+    if (m > 0) {
+      k_rs_faces<true, SMALL><<<dim3((unsigned)fb, (unsigned)b.count), 256, 0, s>>>(
+          faces, m, n, pv.as<RsVert>(), fl.as<uint8_t>(), 0, 0, 0, keys.as<unsigned long long>(), big.as<int>(), rcounters.as<unsigned>(), nullptr, sl);
+      k_rs_big<true><<<dim3(RS_BATCH_BIG_BLOCKS, (unsigned)b.count), 256, 0, s>>>(faces, m, n, pv.as<RsVert>(), 0, 0, keys.as<unsigned long long>(),
+                                                                                  big.as<int>(), rcounters.as<unsigned>(), nullptr, sl);
+    }
+    return hipSuccess;
+  }
+
+  void release() {
+    for (DevBuf* b : {&img, &d_slots, &keys, &pv, &fl, &big, &rcounters}) b->release();
+  }
+};
 
 }  // namespace

@@ -28,12 +28,13 @@
 //                    degenerate and the duplicate faces without an atomic) and of the cluster flags
 //   k_sp_emit_verts  per used cluster: its position (and normal) from the integer sums, its member count
 //   k_sp_vert_dst    per input vertex: the output vertex of its cluster, or -1
-//   k_sp_emit_faces  per kept face: its renumbered canonical triple, its input index
+//   k_mesh_emit_faces  per kept face: its renumbered canonical triple, its input index (sfmx_mesh_dev.h, as clean.hip's)
 // No kernel waits on another workgroup or spins on a memory word.  A face with an index out of range is skipped by every per-face
 // kernel (they all run before the host reads the flag), so nothing is ever accessed through such an index.
 #include <climits>
 
 #include "sfmx_internal.h"
+#include "sfmx_mesh_dev.h"
 
 namespace {
 
@@ -297,17 +298,6 @@ __global__ __launch_bounds__(256) void k_sp_vert_dst(int n, const int* __restric
   vdst[v] = used[id] ? voff[id] : -1;
 }
 
-__global__ __launch_bounds__(256) void k_sp_emit_faces(const int* __restrict__ tri, int m, const int* __restrict__ fkeep,
-                                                       const int* __restrict__ foff, const int* __restrict__ voff,
-                                                       int* __restrict__ faces_out, int* __restrict__ fsrc) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f >= m || !fkeep[f]) return;  // a kept face has a triple of used clusters
-  const size_t o = (size_t)foff[f];
-#pragma unroll
-  for (int a = 0; a < 3; a++) faces_out[3 * o + a] = voff[tri[3 * (size_t)f + a]];
-  fsrc[o] = f;
-}
-
 }  // namespace
 
 struct sfmx_simplify {
@@ -315,7 +305,7 @@ struct sfmx_simplify {
   // two offsets; the scans' partials; the counters and the partial boxes.  grid: per cell occ, off and their scan partials.
   // table: the duplicate table.
   DevBuf work, grid, table;
-  DevBuf in_v, in_n, in_f;  // host inputs, staged
+  MeshInput in;  // host inputs, staged
   DevBuf out_v, out_n, out_f, vdst, fsrc, members;
   bool done = false, has_normals = false;
   int n = 0, m = 0, nv_out = 0, nf_out = 0, clusters = 0, degenerate = 0, duplicates = 0;
@@ -434,7 +424,7 @@ int sp_run(sfmx_ctx* ctx, sfmx_simplify* sp, const double* verts, const double* 
                                         sp->members.as<int>());
     k_sp_vert_dst<<<nbv, 256, 0, s>>>(n, vclu, used, voff, sp->vdst.as<int>());
   }
-  if (m > 0 && n > 0) k_sp_emit_faces<<<nbf, 256, 0, s>>>(tri, m, fkeep, foff, voff, sp->out_f.as<int>(), sp->fsrc.as<int>());
+  if (m > 0 && n > 0) sfmx_mesh_emit_faces(tri, m, fkeep, foff, voff, sp->out_f.as<int32_t>(), sp->fsrc.as<int>(), s);
   SFMX_HIP(ctx, hipGetLastError());
   SFMX_HIP(ctx, sp->t.end(ctx));
   unsigned c[SP_COUNTERS] = {};
@@ -501,9 +491,8 @@ void sfmx_simplify_destroy(sfmx_ctx* ctx, sfmx_simplify* sp) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  for (DevBuf* b : {&sp->work, &sp->grid, &sp->table, &sp->in_v, &sp->in_n, &sp->in_f, &sp->out_v, &sp->out_n, &sp->out_f, &sp->vdst,
-                    &sp->fsrc, &sp->members})
-    b->release();
+  sp->in.release();
+  for (DevBuf* b : {&sp->work, &sp->grid, &sp->table, &sp->out_v, &sp->out_n, &sp->out_f, &sp->vdst, &sp->fsrc, &sp->members}) b->release();
   sp->t.destroy();
   delete sp;
 }
@@ -517,18 +506,9 @@ int sfmx_simplify_run(sfmx_ctx* ctx, sfmx_simplify* sp, const double* verts, con
   SFMX_REQUIRE(ctx, n >= 0 && m >= 0 && n < (1 << 30) && m < (1 << 30) && (n == 0 || verts) && (m == 0 || faces));
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   if (on_device) return sp_run(ctx, sp, verts, normals, n, faces, m, p, n_verts_out, n_faces_out);
-  hipStream_t s = ctx->stream;
-  const size_t vb = (size_t)n * 24, fb = (size_t)m * 12;
-  SFMX_HIP(ctx, sp->in_v.ensure(vb));
-  SFMX_HIP(ctx, sp->in_f.ensure(fb));
-  if (n > 0) SFMX_HIP(ctx, hipMemcpyAsync(sp->in_v.p, verts, vb, hipMemcpyHostToDevice, s));
-  if (m > 0) SFMX_HIP(ctx, hipMemcpyAsync(sp->in_f.p, faces, fb, hipMemcpyHostToDevice, s));
-  if (normals) {
-    SFMX_HIP(ctx, sp->in_n.ensure(vb));
-    if (n > 0) SFMX_HIP(ctx, hipMemcpyAsync(sp->in_n.p, normals, vb, hipMemcpyHostToDevice, s));
-  }
-  return sp_run(ctx, sp, sp->in_v.as<double>(), normals ? sp->in_n.as<double>() : nullptr, n, sp->in_f.as<int32_t>(), m, p, n_verts_out,
-                n_faces_out);
+  MeshDev d;
+  SFMX_HIP(ctx, sp->in.stage(verts, normals, n, faces, m, ctx->stream, d));
+  return sp_run(ctx, sp, d.verts, d.normals, n, d.faces, m, p, n_verts_out, n_faces_out);
 }
 
 int sfmx_simplify_fusion(sfmx_ctx* ctx, sfmx_simplify* sp, const sfmx_fusion* fu, const sfmx_simplify_params* p, int* n_verts_out,

@@ -82,7 +82,8 @@ __global__ __launch_bounds__(256) void k_sm_degree(const unsigned long long* __r
     if (fwd + bwd == 1) c[1]++;
     else c[2]++;
   }
-  et_block_sums<3>(c, counters + SM_EDGE_PART);
+  const int s = sfmx_block_sums(c);
+  if (threadIdx.x < 3) counters[SM_EDGE_PART + 3 * blockIdx.x + threadIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void k_sm_fill(const unsigned long long* __restrict__ keys, size_t slots, const int* __restrict__ row,
@@ -147,7 +148,8 @@ __global__ __launch_bounds__(256) void k_sm_emit(const double* __restrict__ vert
       out[3 * v + k] = (iso || pnd) ? x : o[k] + ((double)Q[3 * v + k] * (1.0 / SM_SCALE)) * unit;
     }
   }
-  et_block_sums<2>(c, counters + SM_VERT_PART);
+  const int s = sfmx_block_sums(c);
+  if (threadIdx.x < 2) counters[SM_VERT_PART + 2 * blockIdx.x + threadIdx.x] = s;
 }
 
 }  // namespace
@@ -156,7 +158,7 @@ struct sfmx_smooth {
   // work: Q (two arrays), cnt, row starts, cursors, the scan's partials, the pinned bytes and the counters.  table: the keys and
   // the two use counters of every slot.  col: the CSR columns.
   DevBuf work, table, col;
-  DevBuf in_v, in_f;  // host inputs, staged; in_f is also the faces _device_mesh hands out for them
+  MeshInput in;  // host inputs, staged; in.in_f is also the faces _device_mesh hands out for them
   DevBuf out_v, flags;
   const int32_t* faces = nullptr;   // the faces of the last successful run, on the device
   const double* normals = nullptr;  // the normals its source carried on the device (_fusion, _clean), or null
@@ -311,7 +313,8 @@ void sfmx_smooth_destroy(sfmx_ctx* ctx, sfmx_smooth* sm) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  for (DevBuf* b : {&sm->work, &sm->table, &sm->col, &sm->in_v, &sm->in_f, &sm->out_v, &sm->flags}) b->release();
+  sm->in.release();
+  for (DevBuf* b : {&sm->work, &sm->table, &sm->col, &sm->out_v, &sm->flags}) b->release();
   sm->t.destroy();
   delete sm;
 }
@@ -324,13 +327,9 @@ int sfmx_smooth_run(sfmx_ctx* ctx, sfmx_smooth* sm, const double* verts, int n, 
   SFMX_REQUIRE(ctx, n >= 0 && m >= 0 && n < (1 << 24) && m < (1 << 30) && (n == 0 || verts) && (m == 0 || faces));
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   if (on_device) return sm_run(ctx, sm, verts, n, faces, m, p);
-  hipStream_t s = ctx->stream;
-  const size_t vb = (size_t)n * 24, fb = (size_t)m * 12;
-  SFMX_HIP(ctx, sm->in_v.ensure(vb));
-  SFMX_HIP(ctx, sm->in_f.ensure(fb));
-  if (n > 0) SFMX_HIP(ctx, hipMemcpyAsync(sm->in_v.p, verts, vb, hipMemcpyHostToDevice, s));
-  if (m > 0) SFMX_HIP(ctx, hipMemcpyAsync(sm->in_f.p, faces, fb, hipMemcpyHostToDevice, s));
-  return sm_run(ctx, sm, sm->in_v.as<double>(), n, sm->in_f.as<int32_t>(), m, p);
+  MeshDev d;
+  SFMX_HIP(ctx, sm->in.stage(verts, nullptr, n, faces, m, ctx->stream, d));
+  return sm_run(ctx, sm, d.verts, n, d.faces, m, p);
 }
 
 int sfmx_smooth_fusion(sfmx_ctx* ctx, sfmx_smooth* sm, const sfmx_fusion* fu, const sfmx_smooth_params* p) {

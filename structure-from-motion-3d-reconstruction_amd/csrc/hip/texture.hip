@@ -6,15 +6,15 @@
 // textured faces out two to a cell of (patch + 1) x patch texels in the order of their indices and bakes every texel of the
 // atlas from the image of its face's camera, bilinearly, at the projection of the texel's point on the face.
 //
-// Exactness: the key image is the renderer's (sfmx_raster_dev.h: the same kernels).  The depth test is visib.hip's two lines,
-// restated here.  The best view is a strict > on int64 areas over views in ascending order, so batches cannot change it; the
+// Exactness: the key image is the renderer's (sfmx_raster_dev.h: the same kernels).  The depth test is visib.hip's: both call
+// rs_vertex_sees.  The best view is a strict > on int64 areas over views in ascending order, so batches cannot change it; the
 // ranks come from a scan; the layout is integer arithmetic on the host; a texel is a fixed sequence of double operations (built
 // with -ffp-contract=off) on values that depend on (face, i, j) alone.  tests/texture_ref.py restates it in NumPy; the tests
-// compare bytes.  The batch size, every grid size, TX_BUDGET and TX_GROUP change the speed only.
+// compare bytes.  The batch size, every grid size, RS_BATCH_BUDGET and TX_GROUP change the speed only.
 //
-// Kernel layout (blocks of 256, the context's stream, no inter-workgroup hand-off, no spinning).  Per batch of at most 64 views,
-// sized as visib.hip sizes it:
-//   k_rs_project / k_rs_faces / k_rs_big <true>   the key images of the batch's views (sfmx_raster_dev.h)
+// Kernel layout (blocks of 256, the context's stream, no inter-workgroup hand-off, no spinning).  Per batch of at most 64 views
+// (sfmx_raster_dev.h: RsViewSet, as visib.hip):
+//   k_rs_project / k_rs_faces / k_rs_big <true>   the key images of the batch's views (RsViewSet::zbuffer)
 //   k_tx_verts    one thread per vertex over the batch's views: one bit per view that sees the vertex
 //   k_tx_faces    one thread per face: the AND of its corners' masks and, per set bit in ascending order, the area A of that
 //                 view; -A > face_area replaces the face's view
@@ -23,11 +23,8 @@
 //   k_scan_*      the exclusive scan of the flags: the ranks (scan.hip)
 //   k_tx_list     rank -> face, and the histogram view_faces
 //   (one read-back of the flag and the number of textured faces; the layout and its refusals on the host)
-//   k_tx_bake     the hot path: one block per group of TX_GROUP cells of one cell row.  The block first stages, per half cell, the
-//                 face's nine doubles and its view's camera, image offset and size in LDS (26 eight-byte words, loaded by 26
-//                 threads each once), then walks the group's texels row by row, thread t on texel t, t + 256, ...: a wave
-//                 stores 64 neighbouring bytes of one atlas row.  Every texel of the atlas is written exactly once, `fill`
-//                 included (also the cells of a partial last row).
+//   k_tx_bake     the hot path: one block per group of TX_GROUP cells of one cell row (sfmx_texture_dev.h: tx_bake, shared with
+//                 k_lv_bake).  Every texel of the atlas is written exactly once, `fill` included.
 //   k_tx_uv       per face: its three corners in half-texels
 // Two host synchronisations per run: after the counts, and at the end.
 #include <cmath>
@@ -39,18 +36,10 @@
 
 namespace {
 
-constexpr size_t TX_BUDGET = (size_t)256 << 20;  // bytes a batch's key slab, per-(view, vertex) records and big-face lists may take
-constexpr int TX_MAX_BATCH = 64;                 // one bit per view in a vertex's mask
-constexpr int TX_BIG_BLOCKS = 64;                // blocks of k_rs_big per view
-constexpr int TX_SMALL = 64;                     // as raster.hip's RS_SMALL
-constexpr int TX_GROUP = 16;                     // cells per block of k_tx_bake
-constexpr int TX_REC = 26;                       // eight-byte words per half cell in LDS
 constexpr int TX_PATCH_MIN = 3, TX_PATCH_MAX = 64, TX_W_MAX = 16384;
 constexpr long long TX_TEXELS_MAX = 1ll << 28;
 
 enum { TX_FLAG = 0, TX_NTEX, TX_NWORDS = 4 };  // int32 words read back
-
-static_assert(sizeof(RsCam) == 16 * 8 && sizeof(RsSlot) == 18 * 8, "k_tx_bake copies a slot as eight-byte words");
 
 __global__ __launch_bounds__(256) void k_tx_verts(const double* __restrict__ verts, int n, const RsSlot* __restrict__ slots, int nb,
                                                   const RsVert* __restrict__ pv, const uint8_t* __restrict__ fl,
@@ -63,28 +52,9 @@ __global__ __launch_bounds__(256) void k_tx_verts(const double* __restrict__ ver
   for (int k = 0; k < nb; k++) {
     const RsSlot& S = slots[k];
     const size_t at = (size_t)k * (size_t)n + (size_t)i;
-    if (!(fl[at] & 2u)) continue;  // not inband
-    const RsVert P = pv[at];
-    const int x = (P.U + 128) >> 8, y = (P.V + 128) >> 8;
-    if (x < 0 || x >= S.cam.w || y < 0 || y >= S.cam.h) continue;
-    const unsigned long long key = keys[S.key_off + ((long long)y * S.cam.w + x)];
-    double p0, p1, p2;
-    const double q2 = rs_depth(S.cam, X0, X1, X2, p0, p1, p2);
-    bool visible = true;
-    if (key != ~0ull) {
-      const double D = (double)__uint_as_float((unsigned)(key >> 32));
-      visible = q2 <= D + depth_tol;  // false for a NaN
-    }
-    if (visible) mk |= 1ull << k;
+    if (rs_vertex_sees(S, pv, fl, keys, at, X0, X1, X2, depth_tol).state == RS_SEES_VISIBLE) mk |= 1ull << k;
   }
   mask[i] = mk;
-}
-
-__device__ __forceinline__ bool tx_face(const int* __restrict__ faces, int f, int n, int& a, int& b, int& c) {
-  a = faces[3 * (size_t)f];
-  b = faces[3 * (size_t)f + 1];
-  c = faces[3 * (size_t)f + 2];
-  return (unsigned)a < (unsigned)n && (unsigned)b < (unsigned)n && (unsigned)c < (unsigned)n;
 }
 
 __global__ __launch_bounds__(256) void k_tx_faces(const int* __restrict__ faces, int m, int n, const RsVert* __restrict__ pv,
@@ -93,7 +63,7 @@ __global__ __launch_bounds__(256) void k_tx_faces(const int* __restrict__ faces,
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= m) return;
   int a, b, c;
-  if (!tx_face(faces, f, n, a, b, c)) return;  // k_tx_mark fails the call; nothing is read through the index
+  if (!mesh_face(faces, f, n, a, b, c)) return;  // k_tx_mark fails the call; nothing is read through the index
   unsigned long long mk = mask[a] & mask[b] & mask[c];
   if (!mk) return;
   long long best = farea[f];
@@ -120,7 +90,7 @@ __global__ __launch_bounds__(256) void k_tx_mark(const int* __restrict__ faces, 
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= m) return;
   int a, b, c;
-  if (!tx_face(faces, f, n, a, b, c)) atomicOr(&words[TX_FLAG], 1);
+  if (!mesh_face(faces, f, n, a, b, c)) atomicOr(&words[TX_FLAG], 1);
   ftex[f] = fview[f] >= 0 ? 1 : 0;
 }
 
@@ -138,81 +108,7 @@ __global__ __launch_bounds__(256) void k_tx_bake(const double* __restrict__ vert
                                                  const int* __restrict__ list, const int* __restrict__ fview,
                                                  const RsSlot* __restrict__ slots, const uint8_t* __restrict__ img, TxLayout lay,
                                                  uint8_t* __restrict__ atlas) {
-  __shared__ double rec[2 * TX_GROUP][TX_REC];  // X a, b, c (9), the camera (16 words), the image's offset
-  __shared__ int idx[2 * TX_GROUP][4];          // the face's corners and its view, -1: a half without a face
-  const int S = lay.S, L = S - 2, row = blockIdx.x, g0 = blockIdx.y * TX_GROUP;
-  const int gc = min(TX_GROUP, lay.C - g0);  // cells of this group
-  if (threadIdx.x < 2 * TX_GROUP) {
-    const int hl = threadIdx.x, c = row * lay.C + g0 + (hl >> 1);
-    const long long r = 2ll * c + (hl & 1);
-    int v = -1, a = 0, b = 0, cc = 0;
-    if ((hl >> 1) < gc && c < lay.cells && c != lay.fill_cell && r < lay.n_tex) {
-      const int f = list[r];
-      v = fview[f];
-      a = faces[3 * (size_t)f];  // a textured face has passed the range check
-      b = faces[3 * (size_t)f + 1];
-      cc = faces[3 * (size_t)f + 2];
-    }
-    idx[hl][0] = a;
-    idx[hl][1] = b;
-    idx[hl][2] = cc;
-    idx[hl][3] = v;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 2 * TX_GROUP * TX_REC; e += 256) {
-    const int hl = e / TX_REC, j = e % TX_REC, v = idx[hl][3];
-    if (v < 0) continue;
-    unsigned long long x;  // bits: the camera's last word is its two ints
-    if (j < 9) {
-      x = reinterpret_cast<const unsigned long long*>(verts)[3 * (size_t)idx[hl][j / 3] + (j % 3)];
-    } else {
-      const unsigned long long* s = reinterpret_cast<const unsigned long long*>(slots + v);  // words 0 .. 15 the camera, 16 key_off, 17 img_off
-      x = s[j == TX_REC - 1 ? 17 : j - 9];
-    }
-    reinterpret_cast<unsigned long long*>(rec[hl])[j] = x;
-  }
-  __syncthreads();
-  const int rw = gc * (S + 1), total = rw * S;
-  const size_t base = (size_t)row * S * lay.W + (size_t)g0 * (S + 1);
-  for (int t = threadIdx.x; t < total; t += 256) {
-    const int ly = t / rw, x = t - ly * rw;
-    const int cb = x / (S + 1), lx = x - cb * (S + 1);
-    const int half = lx + ly >= S ? 1 : 0;
-    const int i = half ? S - lx : lx, j = half ? S - 1 - ly : ly;
-    const int hl = 2 * cb + half;
-    int out = lay.fill;
-    if (idx[hl][3] >= 0) {
-      const double* r = rec[hl];
-      const int i2 = min(i, L), j2 = min(j, L - i2);
-      const double wa = (double)(L - i2 - j2), wb = (double)i2, wc = (double)j2, dl = (double)L;
-      const double X0 = ((wa * r[0] + wb * r[3]) + wc * r[6]) / dl;
-      const double X1 = ((wa * r[1] + wb * r[4]) + wc * r[7]) / dl;
-      const double X2 = ((wa * r[2] + wb * r[5]) + wc * r[8]) / dl;
-      const double* R = r + 9;  // R[0 .. 8], c = R[9 .. 11], f, cx, cy = R[12 .. 14]
-      const double p0 = X0 - R[9], p1 = X1 - R[10], p2 = X2 - R[11];
-      const double q0 = (R[0] * p0 + R[1] * p1) + R[2] * p2;
-      const double q1 = (R[3] * p0 + R[4] * p1) + R[5] * p2;
-      const double q2 = (R[6] * p0 + R[7] * p1) + R[8] * p2;
-      const double u = (R[12] * q0) / q2 + R[13], v = (R[12] * q1) / q2 + R[14];
-      if (q2 > 0.0 && isfinite(u) && isfinite(v)) {
-        const int2 wh = *reinterpret_cast<const int2*>(r + 24);
-        const long long off = *reinterpret_cast<const long long*>(r + 25);
-        const int w = wh.x, h = wh.y;
-        const double uc = fmin(fmax(u, -1.0), (double)w), vc = fmin(fmax(v, -1.0), (double)h);
-        const double x0 = floor(uc), y0 = floor(vc);
-        const double ax = uc - x0, ay = vc - y0;
-        const int xi0 = min(max((int)x0, 0), w - 1), xi1 = min(max((int)x0 + 1, 0), w - 1);
-        const int yi0 = min(max((int)y0, 0), h - 1), yi1 = min(max((int)y0 + 1, 0), h - 1);
-        const uint8_t* I0 = img + off + (long long)yi0 * w;
-        const uint8_t* I1 = img + off + (long long)yi1 * w;
-        const double top = (1.0 - ax) * (double)I0[xi0] + ax * (double)I0[xi1];
-        const double bot = (1.0 - ax) * (double)I1[xi0] + ax * (double)I1[xi1];
-        const double g = (1.0 - ay) * top + ay * bot;
-        out = (int)fmin(255.0, floor(g + 0.5));
-      }
-    }
-    atlas[base + (size_t)ly * lay.W + x] = (uint8_t)out;
-  }
+  tx_bake<false>(verts, faces, list, fview, nullptr, slots, img, lay, atlas);
 }
 
 __global__ __launch_bounds__(256) void k_tx_uv(int m, const int* __restrict__ fview, const int* __restrict__ rank, TxLayout lay,
@@ -240,39 +136,6 @@ __global__ __launch_bounds__(256) void k_tx_uv(int m, const int* __restrict__ fv
   }
 }
 
-struct TxBatch {
-  int first, count;
-};
-
-}  // namespace
-
-namespace {
-
-std::vector<TxBatch> tx_plan(const sfmx_texture* tx, int n, int m, size_t& key_px, int& widest) {
-  std::vector<TxBatch> out;
-  const int V = (int)tx->views.size();
-  key_px = 0;
-  widest = 0;
-  int k = 0;
-  while (k < V) {
-    size_t bytes = 0, px = 0;
-    int c = 0;
-    while (k + c < V && c < TX_MAX_BATCH) {
-      const size_t p = (size_t)tx->views[k + c].w * (size_t)tx->views[k + c].h;
-      const size_t one = p * 8 + (size_t)n * 17 + (size_t)m * 4;
-      if (tx->forced_batch ? c >= tx->forced_batch : (c > 0 && bytes + one > TX_BUDGET)) break;
-      bytes += one;
-      px += p;
-      c++;
-    }
-    out.push_back({k, c});
-    key_px = px > key_px ? px : key_px;
-    widest = c > widest ? c : widest;
-    k += c;
-  }
-  return out;
-}
-
 // the layout from the counts; false when the atlas would be too wide or too large
 bool tx_layout(int n_tex, int n_un, const sfmx_texture_params* p, TxLayout& lay) {
   const int S = p->patch;
@@ -297,21 +160,14 @@ bool tx_layout(int n_tex, int n_un, const sfmx_texture_params* p, TxLayout& lay)
 // verts / faces are device pointers
 int tx_run(sfmx_ctx* ctx, sfmx_texture* tx, const double* verts, int n, const int32_t* faces, int m, const sfmx_texture_params* p) {
   hipStream_t s = ctx->stream;
-  const int V = (int)tx->views.size();
+  RsViewSet& vs = tx->vs;
+  const int V = vs.view_count();
   SFMX_REQUIRE(ctx, V >= 1);
-  for (long long o : tx->img_off) SFMX_REQUIRE(ctx, o >= 0 && "every view needs an image");
+  for (long long o : vs.img_off) SFMX_REQUIRE(ctx, o >= 0 && "every view needs an image");
   const size_t nn = (size_t)n, mm = (size_t)m;
-  size_t key_px = 0;
-  int widest = 0;
-  const std::vector<TxBatch> plan = tx_plan(tx, n, m, key_px, widest);
   const unsigned nbv = (unsigned)((nn + 255) / 256), nbf = (unsigned)((mm + 255) / 256);
-  const int fb = m > (RS_FACE_BLOCKS - 1) * 256 ? RS_FACE_BLOCKS : (m + 255) / 256;
 
-  SFMX_HIP(ctx, tx->keys.ensure(key_px * 8));
-  SFMX_HIP(ctx, tx->pv.ensure((size_t)widest * nn * sizeof(RsVert)));
-  SFMX_HIP(ctx, tx->fl.ensure((size_t)widest * nn));
-  SFMX_HIP(ctx, tx->big.ensure((size_t)widest * mm * 4));
-  SFMX_HIP(ctx, tx->rcounters.ensure((size_t)TX_MAX_BATCH * RS_NWORDS * 4));
+  if (const int rc = vs.prepare(ctx, n, m)) return rc;
   // work: mask u64 [n], then int32: ftex, rank, list [m], the scan's aux
   const size_t aux = sfmx_scan_aux(m > 0 ? m : 1);
   SFMX_HIP(ctx, tx->work.ensure(nn * 8 + (3 * mm + aux) * 4));
@@ -327,21 +183,6 @@ int tx_run(sfmx_ctx* ctx, sfmx_texture* tx, const double* verts, int n, const in
   int* ax = list + mm;
   int* words = tx->res.as<int>();
 
-  // the slots of all views: a batch's key images lie back to back in the key slab
-  tx->slots.resize((size_t)V);
-  for (const TxBatch& b : plan) {
-    long long at = 0;
-    for (int k = b.first; k < b.first + b.count; k++) {
-      tx->slots[k].cam = rs_cam(&tx->views[k]);
-      tx->slots[k].key_off = at;
-      tx->slots[k].img_off = tx->img_off[k];
-      at += (long long)tx->views[k].w * tx->views[k].h;
-    }
-  }
-  SFMX_HIP(ctx, tx->d_slots.ensure(sizeof(RsSlot) * (size_t)V));
-  SFMX_HIP(ctx, hipMemcpyAsync(tx->d_slots.p, tx->slots.data(), sizeof(RsSlot) * (size_t)V, hipMemcpyHostToDevice, s));
-  const RsSlot* d_slots = tx->d_slots.as<RsSlot>();
-
   SFMX_HIP(ctx, tx->t.begin(ctx));
   SFMX_HIP(ctx, hipMemsetAsync(tx->res.p, 0, TX_NWORDS * 4, s));
   SFMX_HIP(ctx, hipMemsetAsync(tx->vfaces.p, 0, (size_t)V * 4, s));
@@ -349,22 +190,12 @@ int tx_run(sfmx_ctx* ctx, sfmx_texture* tx, const double* verts, int n, const in
     SFMX_HIP(ctx, hipMemsetAsync(tx->fview.p, 0xFF, mm * 4, s));
     SFMX_HIP(ctx, hipMemsetAsync(tx->farea.p, 0, mm * 8, s));
   }
-  for (const TxBatch& b : plan) {
+  for (const RsBatch& b : vs.batches) {
     if (n == 0 || m == 0) break;  // nothing to see; a face of a mesh without vertices fails in k_tx_mark
-    size_t px = 0;
-    for (int k = b.first; k < b.first + b.count; k++) px += (size_t)tx->views[k].w * (size_t)tx->views[k].h;
-    const RsSlot* sl = d_slots + b.first;
-    SFMX_HIP(ctx, hipMemsetAsync(tx->keys.p, 0xFF, px * 8, s));
-    SFMX_HIP(ctx, hipMemsetAsync(tx->rcounters.p, 0, (size_t)b.count * RS_NWORDS * 4, s));
-    k_rs_project<true><<<dim3(nbv, (unsigned)b.count), 256, 0, s>>>(verts, n, RsCam{}, sl, p->z_min, tx->pv.as<RsVert>(), tx->fl.as<uint8_t>());
-    k_rs_faces<true, TX_SMALL><<<dim3((unsigned)fb, (unsigned)b.count), 256, 0, s>>>(faces, m, n, tx->pv.as<RsVert>(), tx->fl.as<uint8_t>(), 0, 0, 0,
-                                                                           tx->keys.as<unsigned long long>(), tx->big.as<int>(),
-                                                                           tx->rcounters.as<unsigned>(), nullptr, sl);
-    k_rs_big<true><<<dim3(TX_BIG_BLOCKS, (unsigned)b.count), 256, 0, s>>>(faces, m, n, tx->pv.as<RsVert>(), 0, 0, tx->keys.as<unsigned long long>(),
-                                                                          tx->big.as<int>(), tx->rcounters.as<unsigned>(), nullptr, sl);
-    k_tx_verts<<<nbv, 256, 0, s>>>(verts, n, sl, b.count, tx->pv.as<RsVert>(), tx->fl.as<uint8_t>(), tx->keys.as<unsigned long long>(),
-                                   p->depth_tol, mask);
-    k_tx_faces<<<nbf, 256, 0, s>>>(faces, m, n, tx->pv.as<RsVert>(), mask, b.first, tx->fview.as<int>(), tx->farea.as<long long>());
+    SFMX_HIP(ctx, vs.zbuffer(b, verts, n, faces, m, p->z_min, s));
+    k_tx_verts<<<nbv, 256, 0, s>>>(verts, n, vs.batch_slots(b), b.count, vs.pv.as<RsVert>(), vs.fl.as<uint8_t>(),
+                                   vs.keys.as<unsigned long long>(), p->depth_tol, mask);
+    k_tx_faces<<<nbf, 256, 0, s>>>(faces, m, n, vs.pv.as<RsVert>(), mask, b.first, tx->fview.as<int>(), tx->farea.as<long long>());
   }
   if (m > 0) {
     k_tx_mark<<<nbf, 256, 0, s>>>(faces, m, n, tx->fview.as<int>(), ftex, words);
@@ -385,8 +216,8 @@ int tx_run(sfmx_ctx* ctx, sfmx_texture* tx, const double* verts, int n, const in
   if (lay.cells > 0) {
     const int rows = lay.H / lay.S;
     SFMX_HIP(ctx, tx->tb.begin(ctx));
-    k_tx_bake<<<dim3((unsigned)rows, (unsigned)((lay.C + TX_GROUP - 1) / TX_GROUP)), 256, 0, s>>>(verts, faces, list, tx->fview.as<int>(), d_slots,
-                                                                                              tx->img.as<uint8_t>(), lay, tx->atlas.as<uint8_t>());
+    k_tx_bake<<<dim3((unsigned)rows, (unsigned)((lay.C + TX_GROUP - 1) / TX_GROUP)), 256, 0, s>>>(
+        verts, faces, list, tx->fview.as<int>(), vs.d_slots.as<RsSlot>(), vs.img.as<uint8_t>(), lay, tx->atlas.as<uint8_t>());
     SFMX_HIP(ctx, tx->tb.end(ctx));
     k_tx_uv<<<nbf, 256, 0, s>>>(m, tx->fview.as<int>(), rank, lay, tx->uvh.as<int>());
   }
@@ -405,7 +236,8 @@ int tx_run(sfmx_ctx* ctx, sfmx_texture* tx, const double* verts, int n, const in
   tx->counts[4] = lay.H;
   tx->counts[5] = lay.C;
   tx->lay = lay;
-  tx->last_batch = widest;
+  tx->list = list;
+  vs.last_batch = vs.widest;
   tx->done = true;
   return SFMX_OK;
 }
@@ -450,9 +282,9 @@ void sfmx_texture_destroy(sfmx_ctx* ctx, sfmx_texture* tx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
   }
-  for (DevBuf* b : {&tx->img, &tx->d_slots, &tx->keys, &tx->pv, &tx->fl, &tx->big, &tx->rcounters, &tx->work, &tx->res, &tx->in_v, &tx->in_f,
-                    &tx->fview, &tx->farea, &tx->uvh, &tx->vfaces, &tx->atlas})
-    b->release();
+  tx->vs.release();
+  tx->in.release();
+  for (DevBuf* b : {&tx->work, &tx->res, &tx->fview, &tx->farea, &tx->uvh, &tx->vfaces, &tx->atlas}) b->release();
   tx->t.destroy();
   tx->tb.destroy();
   delete tx;
@@ -460,46 +292,22 @@ void sfmx_texture_destroy(sfmx_ctx* ctx, sfmx_texture* tx) {
 
 int sfmx_texture_reset(sfmx_ctx* ctx, sfmx_texture* tx) {
   SFMX_REQUIRE(ctx, ctx && tx);
-  tx->views.clear();
-  tx->img_off.clear();
-  tx->img_used = 0;
-  return SFMX_OK;
+  return tx->vs.reset();
 }
 
 int sfmx_texture_add_stereo_view(sfmx_ctx* ctx, sfmx_texture* tx, const sfmx_fusion_view* view, const sfmx_stereo* st) {
-  SFMX_REQUIRE(ctx, ctx && tx && st && view);
-  int w = 0, h = 0;
-  const uint8_t* im = sfmx_stereo_device_rect_left(st, &w, &h);
-  SFMX_REQUIRE(ctx, im && view->w == w && view->h == h);
-  return sfmx_texture_add_view(ctx, tx, view, im, 1);
+  SFMX_REQUIRE(ctx, ctx && tx);
+  return tx->vs.add_stereo_view(ctx, view, st);
 }
 
 int sfmx_texture_add_view(sfmx_ctx* ctx, sfmx_texture* tx, const sfmx_fusion_view* view, const uint8_t* image, int on_device) {
-  SFMX_REQUIRE(ctx, ctx && tx && rs_view_ok(view));
-  long long off = -1;
-  if (image) {
-    SFMX_HIP(ctx, hipSetDevice(ctx->device));
-    const long long px = (long long)view->w * view->h;
-    SFMX_REQUIRE(ctx, tx->img_used + px < (1ll << 40));
-    SFMX_HIP(ctx, sfmx_grow_keep(tx->img, (size_t)tx->img_used, (size_t)(tx->img_used + px), ctx->stream));
-    SFMX_HIP(ctx, hipMemcpyAsync(tx->img.as<uint8_t>() + tx->img_used, image, (size_t)px,
-                                 on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    SFMX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller may reuse its buffer
-    off = tx->img_used;
-    tx->img_used += px;
-  }
-  tx->views.push_back(*view);
-  tx->img_off.push_back(off);
-  return SFMX_OK;
+  SFMX_REQUIRE(ctx, ctx && tx);
+  return tx->vs.add_view(ctx, view, image, on_device);
 }
 
-int sfmx_texture_view_count(const sfmx_texture* tx) { return tx ? (int)tx->views.size() : 0; }
+int sfmx_texture_view_count(const sfmx_texture* tx) { return tx ? tx->vs.view_count() : 0; }
 
-int sfmx_texture_set_batch(sfmx_texture* tx, int k) {
-  if (!tx || k < 0 || k > TX_MAX_BATCH) return SFMX_ERR_INVALID;
-  tx->forced_batch = k;
-  return SFMX_OK;
-}
+int sfmx_texture_set_batch(sfmx_texture* tx, int k) { return tx ? tx->vs.set_batch(k) : SFMX_ERR_INVALID; }
 
 int sfmx_texture_run(sfmx_ctx* ctx, sfmx_texture* tx, const double* verts, int n, const int32_t* faces, int m, int on_device,
                      const sfmx_texture_params* p) {
@@ -512,13 +320,9 @@ int sfmx_texture_run(sfmx_ctx* ctx, sfmx_texture* tx, const double* verts, int n
   SFMX_REQUIRE(ctx, (verts || n == 0) && (faces || m == 0));
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
   if (on_device) return tx_run(ctx, tx, verts, n, faces, m, p);
-  hipStream_t s = ctx->stream;
-  const size_t vbytes = (size_t)n * 24, fbytes = (size_t)m * 12;
-  SFMX_HIP(ctx, tx->in_v.ensure(vbytes));
-  SFMX_HIP(ctx, tx->in_f.ensure(fbytes));
-  if (n > 0) SFMX_HIP(ctx, hipMemcpyAsync(tx->in_v.p, verts, vbytes, hipMemcpyHostToDevice, s));
-  if (m > 0) SFMX_HIP(ctx, hipMemcpyAsync(tx->in_f.p, faces, fbytes, hipMemcpyHostToDevice, s));
-  return tx_run(ctx, tx, tx->in_v.as<double>(), n, tx->in_f.as<int32_t>(), m, p);
+  MeshDev d;
+  SFMX_HIP(ctx, tx->in.stage(verts, nullptr, n, faces, m, ctx->stream, d));
+  return tx_run(ctx, tx, d.verts, n, d.faces, m, p);
 }
 
 int sfmx_texture_read(sfmx_ctx* ctx, sfmx_texture* tx, uint8_t* atlas, int32_t* face_view, int64_t* face_area, int32_t* uv_half,
@@ -565,6 +369,6 @@ double sfmx_texture_last_us(const sfmx_texture* tx) { return tx ? tx->t.us : 0.0
 
 double sfmx_texture_last_bake_us(const sfmx_texture* tx) { return tx ? tx->tb.us : 0.0; }
 
-int sfmx_texture_last_batch(const sfmx_texture* tx) { return tx && tx->done ? tx->last_batch : 0; }
+int sfmx_texture_last_batch(const sfmx_texture* tx) { return tx && tx->done ? tx->vs.last_batch : 0; }
 
 }  // extern "C"

@@ -307,6 +307,44 @@ def test_invalid_inputs_each_followed_by_a_good_call(ctx, tx):
     assert capi.texture_default_params() == dict(z_min=0.0, depth_tol=0.0, **capi.TEXTURE_DEFAULTS)
 
 
+def test_view_set_refusals_agree(ctx):
+    """The visibility and the texture object keep the same kind of view list: the same sequence of bad views, bad batch sizes, a
+    reset and one good view gives the same status and the same view_count() on both at every step, and both then run."""
+    good, img = R.pixel_camera(12, 10), _ramp(12, 10)
+    bad_R = np.array(good["R_rw"], np.float64).copy()
+    bad_R.flat[4] = np.nan
+    steps = [("w = 0", lambda o: o.add_view({**good, "w": 0})), ("w = 4097", lambda o: o.add_view({**good, "w": 4097})),
+             ("f = 0", lambda o: o.add_view({**good, "f": 0.0})), ("f = NaN", lambda o: o.add_view({**good, "f": float("nan")})),
+             ("a NaN in R_rw", lambda o: o.add_view({**good, "R_rw": bad_R})), ("set_batch(-1)", lambda o: o.set_batch(-1)),
+             ("set_batch(65)", lambda o: o.set_batch(65)), ("a good view", lambda o: o.add_view(good, img)), ("reset", lambda o: o.reset()),
+             ("a good view after the reset", lambda o: o.add_view(good, img))]
+
+    def status(fn, o):
+        try:
+            fn(o)
+        except capi.SfmxError as e:
+            return e.status
+        return capi.SFMX_OK
+
+    vb, tx = ctx.visib(), ctx.texture()
+    try:
+        seen = []
+        for what, fn in steps:
+            sv, st = status(fn, vb), status(fn, tx)
+            assert sv == st, f"{what}: visibility says {sv}, texture {st}"
+            assert vb.view_count() == tx.view_count(), what
+            seen.append((sv, vb.view_count()))
+        I, OK = capi.SFMX_ERR_INVALID, capi.SFMX_OK
+        assert seen == [(I, 0)] * 7 + [(OK, 1), (OK, 0), (OK, 1)]
+        v, f = _hand(3)
+        a = vb.run(v, f, 0.5, HAND_TOL, cull=0)
+        b = tx.run(v, f, 0.5, HAND_TOL)
+        assert a["faces_seen"] == b["faces_textured"] == 3
+    finally:
+        vb.close()
+        tx.close()
+
+
 def test_a_non_finite_vertex_is_no_error(tx):
     v, f = _hand(3)
     v = v.copy()

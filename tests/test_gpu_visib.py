@@ -222,6 +222,28 @@ def test_random_soup(vb):
     assert want["faces_seen"] > 300 and want["faces_back_only"] > 300 and want["faces_unseen"] > 300
 
 
+@pytest.mark.parametrize("n,m", [(300, 257), (700, 256), (70000, 65537)])  # the block edge, and the scans' second level
+def test_compaction_agrees_between_clean_and_visibility(ctx, vb, n, m):
+    """Both stages compact a mesh by keep flags.  Where every face is kept (clean without a threshold, visibility without views
+    and min_views = 0) the flags are the same, so the five common arrays must be: byte for byte, and as tests/clean_ref.py has them."""
+    import clean_ref as CR
+    v, f, nrm = CR.soup(n, m, seed=n + m)
+    want = CR.clean(v, f, normals=nrm, min_faces=0, min_permille=0)
+    assert want["n_faces"] == m and 0 < want["n_verts"] < n, "a soup that leaves vertices unreferenced"
+    cl = ctx.clean()
+    try:
+        cl.run(v, f, normals=nrm, min_faces=0, min_permille=0)
+        a = cl.read(normals=True)
+    finally:
+        cl.close()
+    _load(vb, [])
+    b = vb.run(v, f, 0.5, 0.5, normals=nrm, min_views=0)
+    for key in ("verts", "normals", "faces", "vert_src", "face_src"):
+        assert a[key].dtype == b[key].dtype == want[key].dtype and a[key].shape == b[key].shape == want[key].shape, key
+        assert a[key].tobytes() == b[key].tobytes(), f"{key}: clean and visibility differ at n = {n}, m = {m}"
+        assert a[key].tobytes() == want[key].tobytes(), f"{key}: not the reference's at n = {n}, m = {m}"
+
+
 # ---- invalid inputs ----------------------------------------------------------------------------------------------------------
 def test_invalid_inputs_each_followed_by_a_good_call(ctx, vb):
     import torch

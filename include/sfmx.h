@@ -1057,6 +1057,77 @@ double sfmx_level_last_us(const sfmx_level* lv);
 double sfmx_level_last_sweeps_us(const sfmx_level* lv);
 double sfmx_level_last_bake_us(const sfmx_level* lv);
 
+/* ---- the textured mesh rendered back into the cameras: exact photometric error ------------------------------- */
+/* The object holds an ordered list of Q >= 0 views, each a sfmx_fusion_view under the z-buffer's camera rules above (B ignored,
+ * sizes may differ), optionally an image u8 [h][w], and an int tex_view: the index of this camera in the texture object's view
+ * list, or -1 when it is not one of them (a held-out or novel camera).  View q's pixels start at off_q = sum_{p < q} w_p h_p in
+ * every per-pixel output.
+ * Inputs of a run: a mesh; a sfmx_texture tx whose last successful sfmx_texture_run was on this mesh (it supplies face_view,
+ * uv_half, W, H and fill); optionally a sfmx_level lv whose last successful run was on tx: then the atlas A is the levelled one,
+ * otherwise tx's; z_min and background.
+ * Per view q: the key image of the whole mesh at cull = 0, exactly as sfmx_raster_run builds it.
+ * Per pixel (x, y) of view q.  No winner: cls = 0, face = -1, rendered = background.  Otherwise f is the winner, with e0, e1, e2,
+ * r_i, t_i = (double)e_i r_i and s = ((double)e0 r0 + (double)e1 r1) + (double)e2 r2 exactly as in the renderer (s > 0 for a
+ * fragment, so everything below is finite).  A_f > 0 (back-facing): cls = 1, rendered = background.  Else k = face_view[f] < 0:
+ * cls = 2, rendered = fill.  Else cls = 3 if k == tex_view[q], otherwise cls = 4, and with h_i = uv_half[f][i] (int32, as doubles)
+ *   hx = ((t0 h0x + t1 h1x) + t2 h2x) / s;  hy likewise
+ *   a = hx * 0.5 - 0.5;  ac = min(max(a, 0.0), (double)(W - 1));  x0 = floor(ac);  fx = ac - x0
+ *   xi0 = (int)x0;  xi1 = min(xi0 + 1, W - 1);  the same with hy and H: yi0, yi1, fy
+ *   top = (1.0 - fx) A[yi0][xi0] + fx A[yi0][xi1];  bot = (1.0 - fx) A[yi1][xi0] + fx A[yi1][xi1]
+ *   g = (1.0 - fy) top + fy bot;  rendered = (u8)min(255.0, floor(g + 0.5)).
+ * Nothing is contracted.
+ * Error (views with an image only): per pixel of class 3 or 4, d = |rendered - I_q[y][x]|, an integer 0 .. 255.
+ * Results.  Per pixel: rendered u8, cls u8, face int32.  Per view: classes int64 [Q][5], the pixels of each class; stats int64
+ * [Q][2][3], for own (class 3) and cross (class 4) the count, the sum of d and the sum of d d; hist int64 [Q][2][256], the
+ * histogram of d.  A view without an image has zero stats and hist.
+ * The keys are the renderer's, a pixel's values are a fixed double sequence on (face, pixel) alone, written by exactly one thread,
+ * and all sums are integer adds, so every byte equals the NumPy restatement in tests/photo_ref.py whatever the schedule, the batch
+ * size and the order of the views. */
+typedef struct sfmx_photo sfmx_photo;  /* the views, their images, the work buffers and the last result; they grow and are kept */
+typedef struct sfmx_photo_params {
+  double z_min;       /* the z-buffer's; finite, > 0; no default */
+  uint8_t background; /* rendered of a pixel without a winner or with a back-facing one (default 0) */
+} sfmx_photo_params;
+void sfmx_photo_default_params(sfmx_photo_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_photo_check_params(const sfmx_photo_params* p);
+int sfmx_photo_create(sfmx_ctx* ctx, sfmx_photo** out);
+void sfmx_photo_destroy(sfmx_ctx* ctx, sfmx_photo* ph);
+/* drops the views and their images and keeps the memory (and the last result) */
+int sfmx_photo_reset(sfmx_ctx* ctx, sfmx_photo* ph);
+/* appends a view; image u8 [h][w] or NULL, a host pointer or (on_device = 1) a device pointer, copied into the object;
+ * tex_view >= -1 (its upper end is checked by the run, which knows the texture object) */
+int sfmx_photo_add_view(sfmx_ctx* ctx, sfmx_photo* ph, const sfmx_fusion_view* view, const uint8_t* image, int on_device, int tex_view);
+/* appends all of tx's views with their images, device to device, view k with tex_view = k */
+int sfmx_photo_add_texture_views(sfmx_ctx* ctx, sfmx_photo* ph, const sfmx_texture* tx);
+int sfmx_photo_view_count(const sfmx_photo* ph);
+/* as sfmx_visib_set_batch: k >= 1 (<= 64) forces k views per batch, 0 restores the automatic size; the result does not depend
+ * on it */
+int sfmx_photo_set_batch(sfmx_photo* ph, int k);
+/* verts double [n][3], faces int32 [m][3]: host pointers (copied into the object) or (on_device = 1) device pointers (read in
+ * place; they must stay until the call returns); lv may be NULL.  SFMX_ERR_INVALID for a tx without a successful run, n or m
+ * other than that run's, an lv without a successful run or with another W or H, a tex_view outside [-1, V), a face index outside
+ * [0, n) (found on the device without any access through it), views of more than 2^28 pixels in all (decided before any
+ * allocation) and parameters outside their range; the object stays usable and a failed call leaves no result.  Q = 0, m = 0 and
+ * a view that hits nothing are not errors.  tx and lv are not modified. */
+int sfmx_photo_run(sfmx_ctx* ctx, sfmx_photo* ph, const sfmx_texture* tx, const sfmx_level* lv, const double* verts, int n,
+                   const int32_t* faces, int m, int on_device, const sfmx_photo_params* p);
+/* the last successful run to the host: rendered u8, cls u8, face int32 [sum w h], classes int64 [Q][5], stats int64 [Q][2][3],
+ * hist int64 [Q][2][256]; any may be NULL.  SFMX_ERR_INVALID before a successful run. */
+int sfmx_photo_read(sfmx_ctx* ctx, sfmx_photo* ph, uint8_t* rendered, uint8_t* cls, int32_t* face, int64_t* classes, int64_t* stats,
+                    int64_t* hist);
+/* Q and the sum of w h of the last successful run; either may be NULL.  SFMX_ERR_INVALID (and zeros) before one. */
+int sfmx_photo_sizes(const sfmx_photo* ph, int* n_views, int* pixels);
+/* the rendered pixels on the device, the object's own array (view q at off_q); returns the sum of w h, or -1 before a
+ * successful run.  Valid until the next run on ph. */
+int sfmx_photo_device_rendered(const sfmx_photo* ph, const uint8_t** rendered);
+/* device time (us) from the first to the last launch of the last run, and of the k_ph_resolve launches alone, when timing is on
+ * (sfmx_set_timing), else 0 */
+double sfmx_photo_last_us(const sfmx_photo* ph);
+double sfmx_photo_last_resolve_us(const sfmx_photo* ph);
+/* the largest number of views the last successful run put into one batch (a property of the schedule, not of the result) */
+int sfmx_photo_last_batch(const sfmx_photo* ph);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

@@ -73,6 +73,10 @@ SYMBOLS = [
     "sfmx_level_default_params", "sfmx_level_check_params", "sfmx_level_create", "sfmx_level_destroy", "sfmx_level_run",
     "sfmx_level_read", "sfmx_level_counts", "sfmx_level_device_atlas", "sfmx_level_last_us", "sfmx_level_last_sweeps_us",
     "sfmx_level_last_bake_us",
+    "sfmx_photo_default_params", "sfmx_photo_check_params", "sfmx_photo_create", "sfmx_photo_destroy", "sfmx_photo_reset",
+    "sfmx_photo_add_view", "sfmx_photo_add_texture_views", "sfmx_photo_view_count", "sfmx_photo_set_batch", "sfmx_photo_run",
+    "sfmx_photo_read", "sfmx_photo_sizes", "sfmx_photo_device_rendered", "sfmx_photo_last_us", "sfmx_photo_last_resolve_us",
+    "sfmx_photo_last_batch",
 ]
 
 
@@ -524,6 +528,72 @@ def level_check_params(**kw) -> bool:
     return load_library().sfmx_level_check_params(byref(level_params(**kw))) == SFMX_OK
 
 
+class PhotoParams(ctypes.Structure):
+    _fields_ = [("z_min", c_double), ("background", c_uint8)]
+
+
+# z_min has no default (a depth in the mesh's units)
+PHOTO_DEFAULTS = dict(background=0)
+PHOTO_CLASSES = ("empty", "back", "untextured", "own", "cross")
+PHOTO_MAX_PIXELS = 1 << 28  # the sum of w h over the views
+
+
+def photo_params(z_min=0.0, **kw) -> PhotoParams:
+    unknown = set(kw) - set(PHOTO_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown photo parameters {sorted(unknown)}")
+    kw = {**PHOTO_DEFAULTS, **kw}
+    if int(kw["background"]) != kw["background"]:
+        raise TypeError("photo parameter background is an integer")
+    if not 0 <= int(kw["background"]) <= 255:
+        raise ValueError(f"background = {kw['background']} is not a byte")
+    return PhotoParams(float(z_min), int(kw["background"]))
+
+
+def photo_default_params() -> dict:
+    """sfmx_photo_default_params as a dict (needs no device)"""
+    p = PhotoParams()
+    load_library().sfmx_photo_default_params(byref(p))
+    return dict(z_min=p.z_min, background=p.background)
+
+
+def photo_check_params(z_min=0.0, **kw) -> bool:
+    """True if sfmx_photo_run would accept the parameters; needs no device"""
+    return load_library().sfmx_photo_check_params(byref(photo_params(z_min, **kw))) == SFMX_OK
+
+
+def _photo_measures(stats3, hist256) -> dict:
+    cnt, sd, sd2 = (int(x) for x in stats3)
+    if cnt == 0:
+        return dict(count=0, mae=None, rmse=None, psnr=None, p90=None)
+    # the 90th percentile: the smallest d with at least 0.9 count pixels at or below it (integers: 10 cum >= 9 count)
+    cum, p90 = 0, 255
+    for d in range(256):
+        cum += int(hist256[d])
+        if 10 * cum >= 9 * cnt:
+            p90 = d
+            break
+    import math
+    return dict(count=cnt, mae=sd / cnt, rmse=math.sqrt(sd2 / cnt),
+                psnr=float("inf") if sd2 == 0 else 10.0 * math.log10(255.0 * 255.0 * cnt / sd2), p90=p90)
+
+
+def photo_summary(stats, hist) -> dict:
+    """stats int64 [Q][2][3] and hist int64 [Q][2][256] of a Photo run -> dict(views=[dict(own=, cross=) per view], own=, cross=
+    pooled over the views), each dict(count, mae = sum d / count, rmse, psnr = 10 log10(255^2 count / sum d^2) or inf at 0, p90:
+    the smallest d with 10 cum(d) >= 9 count); None where count is 0.  Plain Python arithmetic on the integers."""
+    stats = np.asarray(stats, np.int64).reshape(-1, 2, 3)
+    hist = np.asarray(hist, np.int64).reshape(-1, 2, 256)
+    assert len(stats) == len(hist)
+    views = [dict(own=_photo_measures(stats[q, 0], hist[q, 0]), cross=_photo_measures(stats[q, 1], hist[q, 1])) for q in range(len(stats))]
+    pooled = {}
+    for o, name in enumerate(("own", "cross")):
+        st = [sum(int(stats[q, o, j]) for q in range(len(stats))) for j in range(3)]
+        hs = [sum(int(hist[q, o, d]) for q in range(len(hist))) for d in range(256)]
+        pooled[name] = _photo_measures(st, hs)
+    return dict(views=views, **pooled)
+
+
 ALIGN_ITERS_CAP = 64  # SFMX_ALIGN_ITERS_CAP
 ALIGN_CONVERGED, ALIGN_MAX_ITERS, ALIGN_TOO_FEW, ALIGN_DEGENERATE = range(4)
 ALIGN_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")
@@ -618,6 +688,8 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_level_last_us.restype = c_double
         _lib.sfmx_level_last_sweeps_us.restype = c_double
         _lib.sfmx_level_last_bake_us.restype = c_double
+        _lib.sfmx_photo_last_us.restype = c_double
+        _lib.sfmx_photo_last_resolve_us.restype = c_double
     return _lib
 
 
@@ -1692,9 +1764,11 @@ class Texture:
         self.ctx = ctx
         self.h_ = c_void_p()
         ctx._chk(ctx.lib.sfmx_texture_create(ctx.h_, byref(self.h_)))
+        self.shapes = []  # (h, w) of every view
 
     def reset(self):
         self.ctx._chk(self.ctx.lib.sfmx_texture_reset(self.ctx.h_, self.h_))
+        self.shapes = []
 
     def add_view(self, cam: dict, image=None, w=None, h=None):
         """cam: dict(R_rw, c_left, f, cx, cy, w, h) (B is not used; w= / h= override the dict's image size).  image: uint8 [h][w]
@@ -1711,11 +1785,13 @@ class Texture:
             assert image.shape == (h, w), (image.shape, h, w)
             pi = image.ctypes.data_as(c_void_p)
         self.ctx._chk(self.ctx.lib.sfmx_texture_add_view(self.ctx.h_, self.h_, byref(v), pi, c_int(1 if on_dev else 0)))
+        self.shapes.append((h, w))
 
     def add_stereo_view(self, cam: dict, stereo: "Stereo"):
         """the view with the left rectified image of stereo's last disparity call, from where it lies on the device"""
         v = fusion_view({**cam, "B": cam.get("B", 0.0)}, stereo.w, stereo.h)
         self.ctx._chk(self.ctx.lib.sfmx_texture_add_stereo_view(self.ctx.h_, self.h_, byref(v), stereo.h_))
+        self.shapes.append((int(stereo.h), int(stereo.w)))
 
     def view_count(self) -> int:
         return int(self.ctx.lib.sfmx_texture_view_count(self.h_))
@@ -1871,6 +1947,131 @@ class Level:
     def close(self):
         if self.h_:
             self.ctx.lib.sfmx_level_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Photo:
+    """sfmx_photo: the textured mesh rendered back into cameras and compared with their pictures: per pixel the
+    rendered grey, its class (PHOTO_CLASSES) and the visible face; per view the class counts and, for the pixels textured from
+    this view (own) and from another (cross), the count, the sums of |d| and d^2 and the histogram of |d|.  The views, their
+    images and the work buffers are kept between runs."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_photo_create(ctx.h_, byref(self.h_)))
+        self.shapes = []  # (h, w) of every view
+
+    def reset(self):
+        self.ctx._chk(self.ctx.lib.sfmx_photo_reset(self.ctx.h_, self.h_))
+        self.shapes = []
+
+    def add_view(self, cam: dict, image=None, tex_view=-1, w=None, h=None):
+        """cam: dict(R_rw, c_left, f, cx, cy, w, h) (B is not used; w= / h= override the dict's image size).  image: uint8 [h][w]
+        numpy array, an int (device pointer), or None.  tex_view: this camera's index in the texture object's list, or -1."""
+        w, h = int(cam["w"] if w is None else w), int(cam["h"] if h is None else h)
+        v = fusion_view({**cam, "B": cam.get("B", 0.0)}, w, h)
+        on_dev = isinstance(image, int)
+        if image is None:
+            pi = None
+        elif on_dev:
+            pi = c_void_p(image)
+        else:
+            image = np.ascontiguousarray(image, np.uint8)
+            assert image.shape == (h, w), (image.shape, h, w)
+            pi = image.ctypes.data_as(c_void_p)
+        self.ctx._chk(self.ctx.lib.sfmx_photo_add_view(self.ctx.h_, self.h_, byref(v), pi, c_int(1 if on_dev else 0), c_int(int(tex_view))))
+        self.shapes.append((h, w))
+
+    def add_texture_views(self, tx: "Texture"):
+        """appends all of tx's views with their images, device to device, view k with tex_view = k"""
+        assert len(tx.shapes) == tx.view_count(), (len(tx.shapes), tx.view_count())
+        self.ctx._chk(self.ctx.lib.sfmx_photo_add_texture_views(self.ctx.h_, self.h_, tx.h_))
+        self.shapes += tx.shapes
+
+    def view_count(self) -> int:
+        return int(self.ctx.lib.sfmx_photo_view_count(self.h_))
+
+    def set_batch(self, k: int):
+        """k >= 1 forces k views per batch, 0 restores the automatic size; the result does not depend on it"""
+        rc = self.ctx.lib.sfmx_photo_set_batch(self.h_, c_int(int(k)))
+        if rc != SFMX_OK:
+            raise SfmxError(rc, f"sfmx_photo_set_batch: {k} is not in 0 .. {VISIB_MAX_BATCH}")
+
+    def run(self, tx: "Texture", verts, faces, z_min=0.0, lv: "Level" = None, n=None, m=None, read=True, **params):
+        """tx: the Texture whose last run was on this mesh; lv: a Level whose last run was on tx, or None.  verts float64 [n][3]
+        and faces int32 [m][3]: numpy arrays, or ints (device pointers) with n and m given.  z_min is required; params:
+        PHOTO_DEFAULTS keys.  Returns read()'s dict, or sizes() with read=False."""
+        p = photo_params(z_min, **params)
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int):
+            raise TypeError("verts and faces: both host arrays or both device pointers")
+        if on_dev:
+            pv, pf = c_void_p(verts), c_void_p(faces)
+            n, m = int(n), int(m)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            n, m = len(verts), len(faces)
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+        self.ctx._chk(self.ctx.lib.sfmx_photo_run(self.ctx.h_, self.h_, tx.h_, lv.h_ if lv is not None else None, pv, c_int(n), pf, c_int(m),
+                                                  c_int(1 if on_dev else 0), byref(p)))
+        return self.read() if read else self.sizes()
+
+    def sizes(self):
+        """(Q, the sum of w h) of the last successful run; raises before one"""
+        q, px = c_int(0), c_int(0)
+        rc = self.ctx.lib.sfmx_photo_sizes(self.h_, byref(q), byref(px))
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_photo_sizes: no successful run")
+        return q.value, px.value
+
+    def read(self) -> dict:
+        """the last run: dict(rendered u8 / cls u8 / face i32 [sum w h], classes i64 [Q][5], stats i64 [Q][2][3], hist i64
+        [Q][2][256], offsets i64 [Q + 1]: view q's pixels are [offsets[q], offsets[q + 1]))"""
+        Q, px = self.sizes()
+        rendered, cls, face = np.zeros(max(px, 1), np.uint8), np.zeros(max(px, 1), np.uint8), np.zeros(max(px, 1), np.int32)
+        classes, stats, hist = np.zeros((max(Q, 1), 5), np.int64), np.zeros((max(Q, 1), 2, 3), np.int64), np.zeros((max(Q, 1), 2, 256), np.int64)
+        self.ctx._chk(self.ctx.lib.sfmx_photo_read(self.ctx.h_, self.h_, _p(rendered, c_uint8), _p(cls, c_uint8), _p(face, c_int32),
+                                                   classes.ctypes.data_as(c_void_p), stats.ctypes.data_as(c_void_p),
+                                                   hist.ctypes.data_as(c_void_p)))
+        off = np.zeros(Q + 1, np.int64)
+        if len(self.shapes) == Q:
+            off[1:] = np.cumsum([a * b for a, b in self.shapes], dtype=np.int64)
+            assert int(off[-1]) == px, (int(off[-1]), px)
+        return dict(rendered=rendered[:px].copy(), cls=cls[:px].copy(), face=face[:px].copy(), classes=classes[:Q].copy(),
+                    stats=stats[:Q].copy(), hist=hist[:Q].copy(), offsets=off)
+
+    def view_image(self, res: dict, q: int, key="rendered"):
+        """[h][w] of view q out of read()'s dict"""
+        h, w = self.shapes[q]
+        return res[key][int(res["offsets"][q]):int(res["offsets"][q + 1])].reshape(h, w)
+
+    def device_rendered(self):
+        """(the sum of w h, device pointer of the rendered pixels); -1 before a successful run"""
+        a = c_void_p()
+        k = int(self.ctx.lib.sfmx_photo_device_rendered(self.h_, byref(a)))
+        return k, a.value
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_photo_last_us(self.h_))
+
+    def last_resolve_us(self) -> float:
+        return float(self.ctx.lib.sfmx_photo_last_resolve_us(self.h_))
+
+    def last_batch(self) -> int:
+        """the largest number of views the last run put into one batch"""
+        return int(self.ctx.lib.sfmx_photo_last_batch(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_photo_destroy(self.ctx.h_, self.h_)
             self.h_ = c_void_p()
 
     def __del__(self):
@@ -2335,6 +2536,9 @@ class Context:
 
     def level(self) -> "Level":
         return Level(self)
+
+    def photo(self) -> "Photo":
+        return Photo(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

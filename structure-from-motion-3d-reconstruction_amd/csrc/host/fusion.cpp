@@ -127,6 +127,13 @@
 #pragma weak sfmx_level_run
 #pragma weak sfmx_level_read
 #pragma weak sfmx_level_counts
+#pragma weak sfmx_photo_check_params
+#pragma weak sfmx_photo_create
+#pragma weak sfmx_photo_destroy
+#pragma weak sfmx_photo_add_texture_views
+#pragma weak sfmx_photo_run
+#pragma weak sfmx_photo_read
+#pragma weak sfmx_photo_sizes
 
 namespace {
 
@@ -147,7 +154,9 @@ struct Guard {
   sfmx_visib* vb = nullptr;
   sfmx_texture* tx = nullptr;
   sfmx_level* lv = nullptr;
+  sfmx_photo* ph = nullptr;
   ~Guard() {
+    if (ph) sfmx_photo_destroy(ctx, ph);
     if (lv) sfmx_level_destroy(ctx, lv);
     if (tx) sfmx_texture_destroy(ctx, tx);
     if (vb) sfmx_visib_destroy(ctx, vb);
@@ -493,6 +502,33 @@ int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
                              sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_level_request* level, sfmx_fusion_result_ex* res,
                              const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_ph(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts, gt,
+                                  ev, render, align, simplify, simplify_counts, smooth, smooth_counts, fill, fill_counts, raster, visib, texture,
+                                  level, nullptr, res, ply_path, warn, warn_cap);
+}
+
+void sfmx_host_photo_free(sfmx_photo_request* photo) {
+  if (!photo) return;
+  std::free(photo->rendered);
+  std::free(photo->cls);
+  std::free(photo->face);
+  std::free(photo->classes);
+  std::free(photo->stats);
+  std::free(photo->hist);
+  photo->rendered = photo->cls = nullptr;
+  photo->face = nullptr;
+  photo->classes = photo->stats = photo->hist = nullptr;
+}
+
+int sfmx_host_fusion_mesh_ph(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_level_request* level, sfmx_photo_request* photo,
+                             sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -532,6 +568,20 @@ int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on
     if (!&sfmx_level_check_params || !&sfmx_level_create || !&sfmx_level_destroy || !&sfmx_level_run || !&sfmx_level_read || !&sfmx_level_counts)
       return SFMX_ERR_UNSUPPORTED;
     if (!texture || sfmx_level_check_params(&level->params) != SFMX_OK) return SFMX_ERR_INVALID;
+  }
+  sfmx_photo_params pp{};
+  if (photo) {
+    photo->n_views = photo->w = photo->h = 0;
+    photo->rendered = photo->cls = nullptr;
+    photo->face = nullptr;
+    photo->classes = photo->stats = photo->hist = nullptr;
+    if (!&sfmx_photo_check_params || !&sfmx_photo_create || !&sfmx_photo_destroy || !&sfmx_photo_add_texture_views || !&sfmx_photo_run ||
+        !&sfmx_photo_read || !&sfmx_photo_sizes)
+      return SFMX_ERR_UNSUPPORTED;
+    if (!texture) return SFMX_ERR_INVALID;
+    pp = photo->params;
+    pp.z_min = xp.z_min;
+    if (sfmx_photo_check_params(&pp) != SFMX_OK) return SFMX_ERR_INVALID;
   }
   if (!&sfmx_fusion_create || !&sfmx_stereo_disparity) return SFMX_ERR_UNSUPPORTED;
   if (app && (!&sfmx_shade_create || !&sfmx_fusion_extract_normals)) return SFMX_ERR_UNSUPPORTED;
@@ -659,6 +709,10 @@ int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on
   }
   if (level) {
     rc = sfmx_level_create(ctx, &g.lv);
+    if (rc != SFMX_OK) return rc;
+  }
+  if (photo) {
+    rc = sfmx_photo_create(ctx, &g.ph);
     if (rc != SFMX_OK) return rc;
   }
   std::vector<int16_t> d16((size_t)w * h);  // sfmx_stereo_disparity always returns the map to the host
@@ -958,6 +1012,7 @@ int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on
       sfmx_host_visib_free(visib);
       sfmx_host_texture_free(texture);
       sfmx_host_level_free(level);
+      sfmx_host_photo_free(photo);
       return rc;
     }
     if (nf == 0) {  // nothing left: as a volume without a surface
@@ -1015,6 +1070,28 @@ int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on
       }
       if (rc == SFMX_OK) rc = sfmx_level_read(ctx, g.lv, level->atlas, level->corner_adj, level->corner_sample, level->vertex_views);
     }
+    // the textured mesh is rendered back into the texture's own views, from the atlas the caller will see
+    if (rc == SFMX_OK && photo) {
+      int Q = 0, px = 0;
+      rc = sfmx_photo_add_texture_views(ctx, g.ph, g.tx);
+      if (rc == SFMX_OK) rc = sfmx_photo_run(ctx, g.ph, g.tx, level ? g.lv : nullptr, res->verts, nv, res->faces, nf, 0, &pp);
+      if (rc == SFMX_OK) rc = sfmx_photo_sizes(g.ph, &Q, &px);
+      if (rc == SFMX_OK && (Q != V || (long long)px != (long long)Q * w * h)) rc = SFMX_ERR_INVALID;
+      if (rc == SFMX_OK) {
+        const size_t np = (size_t)px + 1, nq = (size_t)(Q > 0 ? Q : 1);
+        photo->n_views = Q;
+        photo->w = w;
+        photo->h = h;
+        photo->rendered = static_cast<uint8_t*>(std::malloc(np));
+        photo->cls = static_cast<uint8_t*>(std::malloc(np));
+        photo->face = static_cast<int32_t*>(std::malloc(np * sizeof(int32_t)));
+        photo->classes = static_cast<int64_t*>(std::malloc(nq * 5 * sizeof(int64_t)));
+        photo->stats = static_cast<int64_t*>(std::malloc(nq * 6 * sizeof(int64_t)));
+        photo->hist = static_cast<int64_t*>(std::malloc(nq * 512 * sizeof(int64_t)));
+        if (!photo->rendered || !photo->cls || !photo->face || !photo->classes || !photo->stats || !photo->hist) rc = SFMX_ERR_INVALID;
+      }
+      if (rc == SFMX_OK) rc = sfmx_photo_read(ctx, g.ph, photo->rendered, photo->cls, photo->face, photo->classes, photo->stats, photo->hist);
+    }
     if (rc != SFMX_OK) {
       const int keep = res->n_views;
       sfmx_host_fusion_free_ex(res);
@@ -1022,6 +1099,7 @@ int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on
       sfmx_host_visib_free(visib);
       sfmx_host_texture_free(texture);
       sfmx_host_level_free(level);
+      sfmx_host_photo_free(photo);
       return rc;
     }
   }
@@ -1076,6 +1154,7 @@ int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on
       sfmx_host_visib_free(visib);
       sfmx_host_texture_free(texture);
       sfmx_host_level_free(level);
+      sfmx_host_photo_free(photo);
       return rc;
     }
     eval_side(d2, nullptr, gt->params, &ev->n_gt, &ev->comp_within, nullptr, nullptr, nullptr);
@@ -1098,6 +1177,7 @@ int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on
       sfmx_host_visib_free(visib);
       sfmx_host_texture_free(texture);
       sfmx_host_level_free(level);
+      sfmx_host_photo_free(photo);
       return rc;
     }
   }
@@ -1125,6 +1205,7 @@ int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on
       sfmx_host_visib_free(visib);
       sfmx_host_texture_free(texture);
       sfmx_host_level_free(level);
+      sfmx_host_photo_free(photo);
       return rc;
     }
   }

@@ -310,4 +310,32 @@ int sfmx_host_fusion_mesh_lv(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
                              sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_level_request* level, sfmx_fusion_result_ex* res,
                              const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_lv with the textured mesh rendered back into the texture's own views.  photo = NULL:
+// exactly sfmx_host_fusion_mesh_lv.  Otherwise a texture request is required (SFMX_ERR_INVALID without one); the photo stage runs
+// last on the same final mesh, over the texture object's views with their images (view k with tex_view = k), at the texture's
+// z_min, from the levelled atlas with a level request; the mesh, the other requests' outputs and the PLY are what they are without
+// it.  The request's outputs are filled: the views (each w x h, view q's pixels at q w h) and rendered u8, cls u8, face int32
+// [n_views w h], classes int64 [n_views][5], stats int64 [n_views][2][3], hist int64 [n_views][2][256] (malloc'ed here, NULL for
+// an empty surface; release them with sfmx_host_photo_free).
+struct sfmx_photo_request {
+  sfmx_photo_params params;  // z_min is not used: the texture's
+  int32_t n_views, w, h;
+  uint8_t* rendered;
+  uint8_t* cls;
+  int32_t* face;
+  int64_t* classes;
+  int64_t* stats;
+  int64_t* hist;
+};
+void sfmx_host_photo_free(sfmx_photo_request* photo);
+int sfmx_host_fusion_mesh_ph(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_level_request* level, sfmx_photo_request* photo,
+                             sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
 }

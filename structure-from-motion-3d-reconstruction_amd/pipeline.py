@@ -259,6 +259,15 @@ class AlignRequest(ctypes.Structure):
     _fields_ = [("seed", c_int), ("params", capi.AlignParams), ("out", POINTER(capi.AlignResult))]
 
 
+PHOTO_KEYS = ("background", "pgm_prefix")
+
+
+class PhotoRequest(ctypes.Structure):
+    _fields_ = [("params", capi.PhotoParams), ("n_views", c_int), ("w", c_int), ("h", c_int), ("rendered", POINTER(c_ubyte)),
+                ("cls", POINTER(c_ubyte)), ("face", POINTER(c_int)), ("classes", POINTER(ctypes.c_int64)), ("stats", POINTER(ctypes.c_int64)),
+                ("hist", POINTER(ctypes.c_int64))]
+
+
 def write_pgm(path: str, image) -> None:
     """a u8 [h][w] image as a binary PGM (P5)"""
     image = np.ascontiguousarray(image, np.uint8)
@@ -349,7 +358,7 @@ def _split_fusion_params(params: dict):
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
          consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, fill=False, raster=None,
-         visibility=False, texture=False, level=False, **params) -> dict:
+         visibility=False, texture=False, level=False, photo=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -417,7 +426,12 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     view) of a textured face gets an offset in 1/256 grey level, pinned on the vertices where views meet to the mean of the views'
     samples and relaxed elsewhere by `iterations` Jacobi sweeps, and every texel gets the blend of its face's three offsets before
     its rounding.  The dict gains level = dict(atlas u8 [H][W], corner_adj i32 [m][3], corner_sample i32 [m][3], vertex_views i32
-    [n], the capi.LEVEL_COUNTS); texture is unchanged, and with obj_path the written atlas files are the levelled atlas."""
+    [n], the capi.LEVEL_COUNTS); texture is unchanged, and with obj_path the written atlas files are the levelled atlas.
+    photo: True, or dict(background=0, pgm_prefix=None) (needs texture) -- the textured final mesh is rendered back into the texture's
+    own views on the device (z_min is the texture's), from the levelled atlas with level, and compared with their
+    images.  The dict gains photo = dict(rendered u8 / cls u8 / face i32 [V][h][w], classes i64 [V][5], stats i64 [V][2][3], hist
+    i64 [V][2][256], summary = capi.photo_summary's dict).  pgm_prefix writes <prefix>_<q>_photo.pgm.  Everything else is what it
+    is without photo."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -581,6 +595,16 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         if xq is None:
             raise TypeError("level needs texture")
         lq = LevelRequest(capi.level_params(**lkw))
+    pq = None
+    if photo:
+        pkw = {} if photo is True else dict(photo)
+        unknown = set(pkw) - set(PHOTO_KEYS)
+        if unknown:
+            raise TypeError(f"unknown photo parameters {sorted(unknown)}")
+        if xq is None:
+            raise TypeError("photo needs texture")
+        photo_prefix = pkw.pop("pgm_prefix", None)
+        pq = PhotoRequest(capi.photo_params(xq.params.z_min, **pkw))  # the texture's z_min
     aq = None
     if align:
         gkw = {} if align is True else dict(align)
@@ -595,7 +619,22 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if lq is not None:
+        if pq is not None:
+            rc = lib.sfmx_host_fusion_mesh_ph(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None,
+                                              byref(rq) if rq is not None else None, byref(aq) if aq is not None else None,
+                                              byref(mp) if mp is not None else None,
+                                              mcounts.ctypes.data_as(POINTER(c_int)) if mp is not None else None,
+                                              byref(tp) if tp is not None else None,
+                                              tcounts.ctypes.data_as(POINTER(c_int)) if tp is not None else None,
+                                              byref(hp) if hp is not None else None,
+                                              hcounts.ctypes.data_as(POINTER(c_int)) if hp is not None else None,
+                                              byref(zq) if zq is not None else None, byref(vq) if vq is not None else None, byref(xq),
+                                              byref(lq) if lq is not None else None, byref(pq), *tail)
+        elif lq is not None:
             rc = lib.sfmx_host_fusion_mesh_lv(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -733,6 +772,16 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                            corner_sample=np.ctypeslib.as_array(lq.corner_sample, (qm, 3)).astype(np.int32) if qm else np.zeros((0, 3), np.int32),
                            vertex_views=np.ctypeslib.as_array(lq.vertex_views, (qn,)).astype(np.int32) if qm and qn else np.zeros(qn, np.int32),
                            **dict(zip(capi.LEVEL_COUNTS, [int(c) for c in lq.counts])))
+            if pq is not None:
+                pQ, pw, ph_ = int(pq.n_views), int(pq.w), int(pq.h)
+                ppx = pQ * pw * ph_
+                pho = dict(rendered=np.ctypeslib.as_array(pq.rendered, (pQ, ph_, pw)).copy() if ppx else np.zeros((0, 0, 0), np.uint8),
+                           cls=np.ctypeslib.as_array(pq.cls, (pQ, ph_, pw)).copy() if ppx else np.zeros((0, 0, 0), np.uint8),
+                           face=np.ctypeslib.as_array(pq.face, (pQ, ph_, pw)).astype(np.int32) if ppx else np.zeros((0, 0, 0), np.int32),
+                           classes=np.ctypeslib.as_array(pq.classes, (pQ, 5)).astype(np.int64) if pQ else np.zeros((0, 5), np.int64),
+                           stats=np.ctypeslib.as_array(pq.stats, (pQ, 2, 3)).astype(np.int64) if pQ else np.zeros((0, 2, 3), np.int64),
+                           hist=np.ctypeslib.as_array(pq.hist, (pQ, 2, 256)).astype(np.int64) if pQ else np.zeros((0, 2, 256), np.int64))
+                pho["summary"] = capi.photo_summary(pho["stats"], pho["hist"])
             nv, nf = (rex.n_verts, rex.n_faces) if rex.n_faces else (0, 0)
             verts = np.ctypeslib.as_array(rex.verts, (nv, 3)).copy() if nf else np.zeros((0, 3))
             faces = np.ctypeslib.as_array(rex.faces, (nf, 3)).astype(np.int32) if nf else np.zeros((0, 3), np.int32)
@@ -749,6 +798,13 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                 lib.sfmx_host_texture_free(byref(xq))
             if lq is not None:
                 lib.sfmx_host_level_free(byref(lq))
+            if pq is not None:
+                lib.sfmx_host_photo_free(byref(pq))
+        if pq is not None:
+            out["photo"] = pho
+            if photo_prefix:
+                for q in range(len(pho["rendered"])):
+                    write_pgm(f"{photo_prefix}_{q}_photo.pgm", pho["rendered"][q])
         if vq is not None:
             out["visibility"] = vis
         if xq is not None:
@@ -851,7 +907,7 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     pair's view to the volume before it enters it; 'simplify' (True or a dict, as fuse) simplifies the final surface by exact vertex
     clustering; 'smooth' (True or a dict, as fuse) smooths it with the exact Taubin filter first; 'fill' (True or a dict, as fuse) fills its small
     holes before that; 'raster' (a dict, as fuse) renders the final mesh from further cameras; 'visibility' (a dict, as fuse) first removes
-    the faces no pair's camera sees from the front; 'texture' (a dict, as fuse) bakes a texture atlas for the final mesh; 'level' (True or a dict, as fuse, with texture) levels its seams.  The run itself, its log and every other output are unchanged.
+    the faces no pair's camera sees from the front; 'texture' (a dict, as fuse) bakes a texture atlas for the final mesh; 'level' (True or a dict, as fuse, with texture) levels its seams; 'photo' (True or a dict, as fuse, with texture) renders the textured mesh back into the texture's views and measures the photometric error.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -925,10 +981,11 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         visibility = fz.pop("visibility", False)
         texture = fz.pop("texture", False)
         level = fz.pop("level", False)
+        photo = fz.pop("photo", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
                                  appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align,
                                  simplify=simplify, smooth=smooth, fill=fill, raster=raster, visibility=visibility, texture=texture,
-                                 level=level, **fz)
+                                 level=level, photo=photo, **fz)
     return out
 
 

@@ -619,6 +619,101 @@ int sfmx_align_stereo_view(sfmx_ctx* ctx, sfmx_align* al, sfmx_fusion* fu, const
 /* device time (us) of the evaluations of the last call when timing is on (sfmx_set_timing), else 0 */
 double sfmx_align_last_us(const sfmx_align* al);
 
+/* ---- registering a surface to a reference mesh: Sim(3) point-to-plane Gauss-Newton ------------------------- */
+/* Everything is IEEE double in the written order, nothing is contracted, and sqrt is taken on the host only.
+ *   transform T = (s, R[3][3], t[3]); identity = (1.0, I, 0)
+ *   apply:      y_a = s*((R_a0*x0 + R_a1*x1) + R_a2*x2) + t_a
+ *   target:     V double [nv][3], F int32 [m][3], d_max (and cell) exactly as sfmx_sdist_set_target takes them (same refusals)
+ *   pivot:      p_a = 0.5*(min_a + max_a) over the target vertices that a face uses; min and max are taken in the order of the
+ *               finite doubles with -0.0 below +0.0, so any reduction order gives the same bits; a target with m = 0 has
+ *               pivot 0 and every evaluation has n_used = 0
+ *   samples:    source points X double [n][3]; sample k = 0 .. ns-1, ns = ceil(n/stride), is point i = stride*k
+ *   per sample: y = apply(T, x_i); (d2, f) = the sdist query of y against the target (unchanged)
+ *               used iff f >= 0 and nn > 0, with a, b, c = V[F[f]]; u = b-a; v = c-a; n = cross(u, v) and nn = dot(n, n) in
+ *               sfmx_sdist_math.h's own expressions
+ *               h = dot(y-a, n); q = y - p; w = 1.0/nn
+ *               J = (q1*n2 - q2*n1, q2*n0 - q0*n2, q0*n1 - q1*n0, n0, n1, n2, dot(q, n))
+ *   terms (37, this order): A_mn = (J_m*J_n)*w for m <= n row by row (28); b_m = (J_m*h)*w (7); e = (h*h)*w (1); c = d2 (1);
+ *               an unused sample contributes +0.0 to all 37; n_used = used samples (int32)
+ *   ordered sum: the tree of the view alignment above with rows of 37: sample k is in block k/256, lane = k%64,
+ *               wave = (k%256)/64, tree index 4*lane + wave; block partials in groups of 256 rows, recursively, padding +0.0;
+ *               ns = 0 gives 37 times +0.0
+ *   solve (host): that stage's Cholesky, forward and backward substitution at dimension 7 (with_scale) or 6 (rows / columns
+ *               0..5 only), M_mm = A_mm + damping; a pivot d <= 0 or not finite: DEGENERATE
+ *               omega = delta[0:3], v = delta[3:6], sigma = delta[6] (0.0 without scale)
+ *   update:     D = that stage's Cayley matrix of omega, element by element; g = 1.0 + sigma; !(g > 0): DEGENERATE
+ *               s' = g*s; R'_ab = (D_a0*R_0b + D_a1*R_1b) + D_a2*R_2b; u = t - p
+ *               t'_a = (p_a + g*((D_a0*u0 + D_a1*u1) + D_a2*u2)) + v_a
+ *               a T' with a non-finite entry or !(s' > 0) (overflow, underflow): DEGENERATE
+ *   loop:       at most max_iters evaluations, starting from init (identity when NULL).  n_used < min_points: TOO_FEW.
+ *               Otherwise step; CONVERGED when, after the update, |omega| <= eps_rot and fabs(sigma) <= eps_scale and
+ *               |v| <= eps_trans*d_max (|x| = sqrt((x0*x0 + x1*x1) + x2*x2)).  Out of evaluations: MAX_ITERS.
+ *               TOO_FEW / DEGENERATE return the last transform whose evaluation gave a step (init if none did).
+ *               trace per evaluation: n_used, e, c, |omega|, |v|, sigma (zeros when no step was taken)
+ * (h*h)/nn is the squared distance to the plane of the face sdist names (the smallest index among those attaining the minimum),
+ * even where the nearest point lies on its edge or corner; a correspondence is dropped exactly when sdist clips it, so d_max is
+ * the trimming distance.  c only gives the point-to-point RMS sqrt(c/n_used) of the trace.  Sums, n_used, the pivot and every
+ * iterate are bit-identical to the NumPy restatement in tests/register_ref.py. */
+#define SFMX_REGISTER_ITERS_CAP 64 /* max_iters, and the length of the trace */
+#define SFMX_REGISTER_TERMS 37
+enum { SFMX_REGISTER_CONVERGED = 0, SFMX_REGISTER_MAX_ITERS = 1, SFMX_REGISTER_TOO_FEW = 2, SFMX_REGISTER_DEGENERATE = 3 };
+typedef struct sfmx_register sfmx_register;  /* an sdist object with the target, and device work buffers; they grow on demand */
+typedef struct sfmx_register_params {
+  double d_max;     /* the trimming distance, as sfmx_sdist_params.d_max; no default */
+  double cell;      /* as sfmx_sdist_params.cell (default 0) */
+  int max_iters;    /* evaluations at most, 1 .. 64 (default 20) */
+  int stride;       /* every stride-th source point is a sample, >= 1 (default 1) */
+  int min_points;   /* fewer used samples than this end the loop with TOO_FEW, >= 7 (default 16) */
+  int with_scale;   /* 1 (default): seven parameters; 0: six, the scale stays */
+  double damping;   /* added to the diagonal of A, >= 0 (default 0) */
+  double eps_rot;   /* converged when |omega| <= eps_rot (default 1e-4) ... */
+  double eps_scale; /* ... and fabs(sigma) <= eps_scale (default 1e-4) ... */
+  double eps_trans; /* ... and |v| <= eps_trans * d_max (default 1e-3); all three >= 0 and finite */
+} sfmx_register_params;
+typedef struct sfmx_register_transform {
+  double s;    /* > 0 */
+  double R[9]; /* row-major */
+  double t[3];
+} sfmx_register_transform;
+typedef struct sfmx_register_result {
+  sfmx_register_transform T; /* source -> target */
+  int status;                /* SFMX_REGISTER_CONVERGED, _MAX_ITERS, _TOO_FEW or _DEGENERATE */
+  int iterations;            /* evaluations made */
+  int32_t n[SFMX_REGISTER_ITERS_CAP];    /* per evaluation: samples used ... */
+  double e[SFMX_REGISTER_ITERS_CAP];     /* ... sum (h h) / nn ... */
+  double c[SFMX_REGISTER_ITERS_CAP];     /* ... sum d2 ... */
+  double rot[SFMX_REGISTER_ITERS_CAP];   /* ... |omega| of the step taken (0 when none was) ... */
+  double trans[SFMX_REGISTER_ITERS_CAP]; /* ... |v| ... */
+  double sigma[SFMX_REGISTER_ITERS_CAP]; /* ... and sigma */
+} sfmx_register_result;
+void sfmx_register_default_params(sfmx_register_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_register_check_params(const sfmx_register_params* p);
+int sfmx_register_create(sfmx_ctx* ctx, sfmx_register** out);
+void sfmx_register_destroy(sfmx_ctx* ctx, sfmx_register* rg);
+/* as sfmx_sdist_set_target with p's d_max and cell (host pointers, or device pointers with on_device = 1; copied), every
+ * refusal of it included; p is checked as a whole.  A failed call leaves no target; the object stays usable. */
+int sfmx_register_set_target(sfmx_ctx* ctx, sfmx_register* rg, const double* verts, int nv, const int32_t* faces, int m, int on_device,
+                             const sfmx_register_params* p);
+/* the pivot of the current target; SFMX_ERR_INVALID (and zeros) without one; needs no context */
+int sfmx_register_pivot(const sfmx_register* rg, double* pivot3);
+/* one evaluation at T (identity when NULL), no step: sums double [37] and *n_used.  points double [n][3], a host pointer or
+ * (on_device = 1) a device pointer, 0 <= n < 2^30.  SFMX_ERR_INVALID, with the target kept, before a successful set_target, for
+ * a sampled source coordinate (or its transform) that is not finite, a T with non-finite entries or s <= 0, bad parameters, and
+ * a d_max or cell other than the target's. */
+int sfmx_register_system(sfmx_ctx* ctx, sfmx_register* rg, const double* points, int n, int on_device, const sfmx_register_transform* T,
+                         const sfmx_register_params* p, double* sums, int32_t* n_used);
+/* the loop from init (identity when NULL); the statuses are results: the call returns SFMX_OK with them */
+int sfmx_register_run(sfmx_ctx* ctx, sfmx_register* rg, const double* points, int n, int on_device, const sfmx_register_transform* init,
+                      const sfmx_register_params* p, sfmx_register_result* out);
+/* out double [n][3] on the host = apply(T, every point) */
+int sfmx_register_apply(sfmx_ctx* ctx, sfmx_register* rg, const sfmx_register_transform* T, const double* points, int n, int on_device,
+                        double* out);
+/* device time (us) of the last call's own launches (k_rg_apply, k_rg_system, the tree; the pivot's reduction in set_target),
+ * and of its sdist queries (set_target: the target's grid), when timing is on (sfmx_set_timing), else 0 */
+double sfmx_register_last_us(const sfmx_register* rg);
+double sfmx_register_last_query_us(const sfmx_register* rg);
+
 /* ---- simplifying a triangle mesh: exact vertex clustering on a uniform grid --------------------------------- */
 /* Per vertex and component q = (x - origin) / cell, c = floor(q), t = q - c and Q = (int64)floor(t 2^30 + 0.5), in this order in
  * IEEE double without contraction.  A cluster is an occupied cell; clusters are numbered in ascending linear index

@@ -52,6 +52,9 @@ SYMBOLS = [
     "sfmx_raycast_last_samples",
     "sfmx_align_default_params", "sfmx_align_check_params", "sfmx_align_create", "sfmx_align_destroy", "sfmx_align_system",
     "sfmx_align_system_arrays", "sfmx_align_view", "sfmx_align_view_arrays", "sfmx_align_stereo_view", "sfmx_align_last_us",
+    "sfmx_register_default_params", "sfmx_register_check_params", "sfmx_register_create", "sfmx_register_destroy",
+    "sfmx_register_set_target", "sfmx_register_pivot", "sfmx_register_system", "sfmx_register_run", "sfmx_register_apply",
+    "sfmx_register_last_us", "sfmx_register_last_query_us",
     "sfmx_simplify_default_params", "sfmx_simplify_check_params", "sfmx_simplify_create", "sfmx_simplify_destroy", "sfmx_simplify_run",
     "sfmx_simplify_fusion", "sfmx_simplify_clean", "sfmx_simplify_read", "sfmx_simplify_sizes", "sfmx_simplify_counts",
     "sfmx_simplify_device_surface", "sfmx_simplify_device_mesh", "sfmx_simplify_last_us",
@@ -642,6 +645,73 @@ def align_check_params(**kw) -> bool:
     return load_library().sfmx_align_check_params(byref(align_params(**kw))) == SFMX_OK
 
 
+REGISTER_ITERS_CAP = 64  # SFMX_REGISTER_ITERS_CAP
+REGISTER_TERMS = 37      # SFMX_REGISTER_TERMS
+REGISTER_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")
+
+
+class RegisterParams(ctypes.Structure):
+    _fields_ = [("d_max", c_double), ("cell", c_double), ("max_iters", c_int), ("stride", c_int), ("min_points", c_int),
+                ("with_scale", c_int), ("damping", c_double), ("eps_rot", c_double), ("eps_scale", c_double), ("eps_trans", c_double)]
+
+
+class RegisterTransform(ctypes.Structure):
+    _fields_ = [("s", c_double), ("R", c_double * 9), ("t", c_double * 3)]
+
+    def asdict(self) -> dict:
+        return dict(s=float(self.s), R=np.array(self.R[:]).reshape(3, 3), t=np.array(self.t[:]))
+
+
+class RegisterResult(ctypes.Structure):
+    _fields_ = [("T", RegisterTransform), ("status", c_int), ("iterations", c_int), ("n", c_int32 * REGISTER_ITERS_CAP),
+                ("e", c_double * REGISTER_ITERS_CAP), ("c", c_double * REGISTER_ITERS_CAP), ("rot", c_double * REGISTER_ITERS_CAP),
+                ("trans", c_double * REGISTER_ITERS_CAP), ("sigma", c_double * REGISTER_ITERS_CAP)]
+
+    def asdict(self) -> dict:
+        """dict(T=dict(s, R, t), status, iterations, trace=[(n_used, e, c, |omega|, |v|, sigma), ...])"""
+        k = int(self.iterations)
+        return dict(T=self.T.asdict(), status=int(self.status), iterations=k,
+                    trace=[(int(self.n[i]), float(self.e[i]), float(self.c[i]), float(self.rot[i]), float(self.trans[i]),
+                            float(self.sigma[i])) for i in range(k)])
+
+
+# d_max has no default (a length in the caller's units)
+REGISTER_DEFAULTS = dict(cell=0.0, max_iters=20, stride=1, min_points=16, with_scale=1, damping=0.0, eps_rot=1e-4, eps_scale=1e-4,
+                         eps_trans=1e-3)
+
+
+def register_params(d_max, **kw) -> RegisterParams:
+    unknown = set(kw) - set(REGISTER_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown register parameters {sorted(unknown)}")
+    d = {**REGISTER_DEFAULTS, **kw}
+    return RegisterParams(float(d_max), float(d["cell"]), int(d["max_iters"]), int(d["stride"]), int(d["min_points"]),
+                          int(bool(d["with_scale"])), float(d["damping"]), float(d["eps_rot"]), float(d["eps_scale"]), float(d["eps_trans"]))
+
+
+def register_default_params() -> dict:
+    """sfmx_register_default_params as a dict (needs no device)"""
+    p = RegisterParams()
+    load_library().sfmx_register_default_params(byref(p))
+    return {k: getattr(p, k) for k, _ in RegisterParams._fields_}
+
+
+def register_check_params(d_max, **kw) -> bool:
+    """True if the sfmx_register entries would accept the parameters; needs no device"""
+    return load_library().sfmx_register_check_params(byref(register_params(d_max, **kw))) == SFMX_OK
+
+
+def register_transform(T=None) -> RegisterTransform:
+    """T: None (the identity), or dict(s, R [3][3], t [3])"""
+    if T is None:
+        T = dict(s=1.0, R=np.eye(3), t=np.zeros(3))
+    unknown = set(T) - {"s", "R", "t"}
+    if unknown or set(T) != {"s", "R", "t"}:
+        raise TypeError("a transform is dict(s=, R=, t=)")
+    R, t = _f64(T["R"]).reshape(9), _f64(T["t"]).reshape(3)
+    return RegisterTransform(float(T["s"]), (c_double * 9)(*R), (c_double * 3)(*t))
+
+
 def stereo_check_params(w: int, h: int, **kw) -> bool:
     """True if sfmx_stereo_create would accept (w, h, params); needs no device"""
     return load_library().sfmx_stereo_check_params(c_int(w), c_int(h), byref(stereo_params(**kw))) == SFMX_OK
@@ -678,6 +748,8 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_raycast_last_us.restype = c_double
         _lib.sfmx_raycast_last_samples.restype = c_uint64
         _lib.sfmx_align_last_us.restype = c_double
+        _lib.sfmx_register_last_us.restype = c_double
+        _lib.sfmx_register_last_query_us.restype = c_double
         _lib.sfmx_simplify_last_us.restype = c_double
         _lib.sfmx_smooth_last_us.restype = c_double
         _lib.sfmx_fill_last_us.restype = c_double
@@ -2170,6 +2242,103 @@ class Align:
             pass
 
 
+class Register:
+    """sfmx_register: Sim(3) point-to-plane registration of source points to a target mesh.  One target serves
+    many sources; the target's grid and the work buffers are kept between calls."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        self.d_max = None
+        self.cell = 0.0
+        ctx._chk(ctx.lib.sfmx_register_create(ctx.h_, byref(self.h_)))
+
+    def set_target(self, verts, faces, d_max, cell=0.0, nv=None, m=None):
+        """verts float64 [nv][3] and faces int32 [m][3]: numpy arrays, or ints (device pointers) with nv and m given; d_max is
+        the trimming distance of every later call"""
+        p = register_params(d_max, cell=cell)
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int):
+            raise TypeError("verts and faces: both host arrays or both device pointers")
+        if on_dev:
+            pv, pf = c_void_p(verts), c_void_p(faces)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            nv, m = len(verts), len(faces)
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+        self.d_max = None
+        self.ctx._chk(self.ctx.lib.sfmx_register_set_target(self.ctx.h_, self.h_, pv, c_int(nv), pf, c_int(m), c_int(1 if on_dev else 0),
+                                                            byref(p)))
+        self.d_max, self.cell = float(d_max), float(cell)
+
+    def _params(self, params) -> RegisterParams:
+        if "d_max" in params or "cell" in params:
+            raise TypeError("d_max and cell belong to set_target")
+        # without a target the library refuses the call; any valid d_max lets it get that far
+        return register_params(1.0 if self.d_max is None else self.d_max, cell=self.cell, **params)
+
+    @staticmethod
+    def _points(points, n):
+        if isinstance(points, int):
+            return c_void_p(points), int(n), 1, None
+        points = _f64(points).reshape(-1, 3)
+        return points.ctypes.data_as(c_void_p), len(points), 0, points
+
+    def pivot(self) -> np.ndarray:
+        p = np.zeros(3)
+        rc = self.ctx.lib.sfmx_register_pivot(self.h_, _p(p, c_double))
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_register_pivot: no target")
+        return p
+
+    def system(self, points, T=None, n=None, **params):
+        """one evaluation at T (None: the identity), no step: (sums f64 [37] = A row by row upper, b, e, c; n_used).  points:
+        float64 [n][3], or an int (device pointer) with n given.  params: REGISTER_DEFAULTS keys but cell."""
+        p = self._params(params)
+        pp, n, on_dev, keep = self._points(points, n)
+        t = register_transform(T)
+        sums, nu = np.zeros(REGISTER_TERMS), c_int32(0)
+        self.ctx._chk(self.ctx.lib.sfmx_register_system(self.ctx.h_, self.h_, pp, c_int(n), c_int(on_dev), byref(t), byref(p),
+                                                        _p(sums, c_double), byref(nu)))
+        return sums, int(nu.value)
+
+    def run(self, points, init=None, n=None, **params) -> dict:
+        """the Gauss-Newton loop from init (None: the identity): RegisterResult.asdict()"""
+        p = self._params(params)
+        pp, n, on_dev, keep = self._points(points, n)
+        t = register_transform(init) if init is not None else None
+        out = RegisterResult()
+        self.ctx._chk(self.ctx.lib.sfmx_register_run(self.ctx.h_, self.h_, pp, c_int(n), c_int(on_dev), byref(t) if t is not None else None,
+                                                     byref(p), byref(out)))
+        return out.asdict()
+
+    def apply(self, T, points, n=None) -> np.ndarray:
+        """float64 [n][3]: every point moved by T"""
+        pp, n, on_dev, keep = self._points(points, n)
+        t = register_transform(T)
+        out = np.zeros((max(n, 1), 3))
+        self.ctx._chk(self.ctx.lib.sfmx_register_apply(self.ctx.h_, self.h_, byref(t), pp, c_int(n), c_int(on_dev), _p(out, c_double)))
+        return out[:n].copy()
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_register_last_us(self.h_))
+
+    def last_query_us(self) -> float:
+        return float(self.ctx.lib.sfmx_register_last_query_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_register_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Stereo:
     """Device buffers of sfmx_stereo for one (w, h, params); disparity() runs rectify -> census -> SGM -> select -> speckle."""
 
@@ -2524,6 +2693,9 @@ class Context:
 
     def align(self) -> "Align":
         return Align(self)
+
+    def register(self) -> "Register":
+        return Register(self)
 
     def raster(self) -> "Raster":
         return Raster(self)

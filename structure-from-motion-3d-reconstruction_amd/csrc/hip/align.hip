@@ -16,10 +16,12 @@
 //                 and 1) combine the four waves through 28 x 4 doubles of LDS: (p0 + p2) + (p1 + p3).
 //   k_al_tree     the same tree over 256 rows of block partials per workgroup (row r of the group at tree index r, padded with
 //                 +0.0), launched once per level until one row is left.  No floating-point atomics; no workgroup waits on
-//                 another inside a launch.  n is an integer sum, one atomicAdd per wave.
+//                 another inside a launch.  n is an integer sum, one atomicAdd per wave.  The tree's device functions and
+//                 k_al_tree live in sfmx_tree.h, which register.hip shares.
 #include <cmath>
 
 #include "sfmx_internal.h"
+#include "sfmx_tree.h"
 #include "sfmx_tsdf.h"
 #include "sfmx_view.h"
 
@@ -32,16 +34,6 @@ struct AlParams {
   double p[3];  // the pivot: the box centre
   int stride;
 };
-
-// sum of v over the 64 lanes: the tree levels with offsets 128 .. 4 (t = 4 lane + wave); every lane gets the result
-__device__ __forceinline__ double al_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;
-}
-
-// the last two levels (offsets 2 and 1) over the four waves' partials of one term
-__device__ __forceinline__ double al_cross(const double* q) { return (q[0] + q[2]) + (q[1] + q[3]); }
 
 __global__ __launch_bounds__(256) void k_al_system(const double* __restrict__ sum, const int* __restrict__ cnt, FuGrid g, DevView V,
                                                    AlParams P, const int16_t* __restrict__ disp, double* __restrict__ partial,
@@ -137,21 +129,6 @@ __global__ __launch_bounds__(256) void k_al_system(const double* __restrict__ su
   }
 }
 
-// one level of the tree over rows of 28: group = blockIdx.x takes rows [256 group, 256 group + 256), missing rows are +0.0
-__global__ __launch_bounds__(256) void k_al_tree(const double* __restrict__ in, int rows, double* __restrict__ out) {
-  __shared__ double part[AL_TERMS][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long r = (long long)blockIdx.x * 256 + (4 * lane + wave);
-  const bool have = r < (long long)rows;
-#pragma unroll 4
-  for (int t = 0; t < AL_TERMS; t++) {
-    const double v = al_wave_sum(have ? in[(size_t)r * AL_TERMS + t] : 0.0);
-    if (lane == 0) part[t][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < AL_TERMS) out[(size_t)blockIdx.x * AL_TERMS + threadIdx.x] = al_cross(part[threadIdx.x]);
-}
-
 }  // namespace
 
 struct sfmx_align {
@@ -196,7 +173,7 @@ int al_eval(sfmx_ctx* ctx, sfmx_align* al, const AlInput& in, const sfmx_fusion_
   int cur = 0;
   while (rows > 1) {
     const int groups = (rows + 255) / 256;
-    k_al_tree<<<(unsigned)groups, 256, 0, s>>>(al->part[cur].as<double>(), rows, al->part[cur ^ 1].as<double>());
+    k_al_tree<AL_TERMS><<<(unsigned)groups, 256, 0, s>>>(al->part[cur].as<double>(), rows, al->part[cur ^ 1].as<double>());
     SFMX_HIP(ctx, hipGetLastError());
     rows = groups;
     cur ^= 1;

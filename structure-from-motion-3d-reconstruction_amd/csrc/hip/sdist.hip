@@ -526,6 +526,17 @@ int sd_query(sfmx_ctx* ctx, sfmx_sdist* sd, const double* points, int n, double*
 
 }  // namespace
 
+int sfmx_sdist_device_state(const sfmx_sdist* sd, const double** verts, const int32_t** faces, int* n_faces, const double** d2,
+                            const int32_t** face) {
+  const bool ok = sd && sd->ready;
+  if (verts) *verts = ok ? sd->tv.as<double>() : nullptr;
+  if (faces) *faces = ok ? sd->tf.as<int32_t>() : nullptr;
+  if (n_faces) *n_faces = ok ? sd->m : 0;
+  if (d2) *d2 = ok ? sd->out_d2.as<double>() : nullptr;
+  if (face) *face = ok ? sd->out_f.as<int32_t>() : nullptr;
+  return ok ? sd->nv : -1;
+}
+
 extern "C" {
 
 void sfmx_sdist_default_params(sfmx_sdist_params* p) {

@@ -155,6 +155,11 @@ int sfmx_fusion_device_volume(const sfmx_fusion* fu, const double** sum, const i
 // clean.hip: the cleaned mesh of the last successful run on the device (verts double [n'][3], faces int32 [*n_faces][3]);
 // returns n', or -1 before a successful run
 int sfmx_clean_device_mesh(const sfmx_clean* cl, const double** verts, const int32_t** faces, int* n_faces);
+// sdist.hip: the target copy the object holds (verts double [nv][3], faces int32 [*n_faces][3]) and where the last query with
+// n > 0 left its results on the device (d2 double [n], face int32 [n]); any pointer may be NULL.  Returns nv, or -1 without a
+// target.  Valid until the next set_target / query on sd.
+int sfmx_sdist_device_state(const sfmx_sdist* sd, const double** verts, const int32_t** faces, int* n_faces, const double** d2,
+                            const int32_t** face);
 // consist.hip: view i as it was added and its filtered map on the device; false without a current result or with i out of range
 bool sfmx_consist_device_view(const sfmx_consist* cs, int i, sfmx_fusion_view* view, const int16_t** filtered);
 

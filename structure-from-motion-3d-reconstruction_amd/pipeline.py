@@ -327,14 +327,72 @@ def _eval_params(d_max, tau, percentile, cell) -> SurfaceEvalParams:
     return SurfaceEvalParams(float(d_max), float(tau), float(percentile), float(cell))
 
 
-def surface_eval(ctx: capi.Context, verts, faces, gt_verts, gt_faces, d_max=None, tau=None, percentile=90.0, cell=0.0) -> dict:
+REGISTER_KEYS = ("d_max", "init") + tuple(capi.REGISTER_DEFAULTS)
+
+
+def _register_request(register, d_max) -> dict | None:
+    """the keyword arguments of surface_register for a `register` request (None / False, True or a dict); d_max defaults to the
+    evaluation's"""
+    if register is None or register is False:
+        return None
+    rkw = {} if register is True else dict(register)
+    unknown = set(rkw) - set(REGISTER_KEYS)
+    if unknown:
+        raise TypeError(f"unknown register parameters {sorted(unknown)}")
+    rkw.setdefault("d_max", d_max)
+    return rkw
+
+
+def surface_register(ctx: capi.Context, verts, faces, gt_verts, gt_faces, d_max=None, init=None, **params) -> dict:
+    """Registers the reconstruction (verts, faces) to the ground truth (gt_verts, gt_faces) by Sim(3) point-to-plane
+    Gauss-Newton on the device (capi.Register): the source points are the vertices a face uses, the target is the
+    ground-truth mesh, d_max (required, in the ground truth's units) is the trimming distance, init (dict(s, R, t), default the
+    identity) the start.  params: capi.REGISTER_DEFAULTS keys.  Returns dict(T=dict(s, R, t), status, iterations, n (samples
+    used by the last evaluation), rms_plane, rms_point (of that evaluation; nan when n = 0), trace, verts (all vertices moved by
+    T, float64 [nv][3]))."""
+    if d_max is None:
+        raise TypeError("surface registration needs d_max (a length in the ground truth's units; there is no default)")
+    unknown = set(params) - set(capi.REGISTER_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown register parameters {sorted(unknown)}")
+    rv = np.ascontiguousarray(verts, np.float64).reshape(-1, 3)
+    rf = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    if len(rf) and (rf.min() < 0 or rf.max() >= len(rv)):
+        raise ValueError("a face index is outside the vertices")
+    mask = np.zeros(len(rv), bool)
+    mask[rf.ravel()] = True
+    cell = params.pop("cell", 0.0)
+    rg = ctx.register()
+    try:
+        rg.set_target(gt_verts, gt_faces, d_max, cell)
+        res = rg.run(rv[mask], init=init, **params)
+        moved = rg.apply(res["T"], rv)
+    finally:
+        rg.close()
+    n, e, c = res["trace"][-1][:3]
+    nan = float("nan")
+    res.update(n=n, rms_plane=float(np.sqrt(e / n)) if n > 0 else nan, rms_point=float(np.sqrt(c / n)) if n > 0 else nan, verts=moved)
+    return res
+
+
+def surface_eval(ctx: capi.Context, verts, faces, gt_verts, gt_faces, d_max=None, tau=None, percentile=90.0, cell=0.0,
+                 register=None) -> dict:
     """Accuracy and completeness of the reconstruction (verts, faces) against the ground truth (gt_verts, gt_faces), sampled at
     the vertices a face uses; the distances come from the device (capi.Sdist).  accuracy: the distance within
     which `percentile` % of the reconstruction lies of the ground truth (nearest rank; distances are clipped at d_max);
     acc_within / comp_within: vertices within tau; completeness = comp_within / n_gt.  d_max and tau are required, tau <= d_max.
-    Returns dict(accuracy, acc_within, acc_mean, acc_max, n_rec, completeness, comp_within, n_gt)."""
+    Returns dict(accuracy, acc_within, acc_mean, acc_max, n_rec, completeness, comp_within, n_gt).
+    register: None (default), True or dict(d_max=, init=, capi.REGISTER_DEFAULTS keys) -- the reconstruction is first registered
+    to the ground truth (surface_register; its d_max defaults to the evaluation's) and the moved vertices are evaluated; the
+    result gains registration = surface_register's dict without the vertices.  d_max and tau are in the ground truth's units."""
     lib = load_host_library()
     p = _eval_params(d_max, tau, percentile, cell)
+    rkw = _register_request(register, d_max)
+    if rkw is not None:
+        reg = surface_register(ctx, verts, faces, gt_verts, gt_faces, **rkw)
+        out = surface_eval(ctx, reg.pop("verts"), faces, gt_verts, gt_faces, d_max=d_max, tau=tau, percentile=percentile, cell=cell)
+        out["registration"] = reg
+        return out
     rv = np.ascontiguousarray(verts, np.float64).reshape(-1, 3)
     rf = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
     gv = np.ascontiguousarray(gt_verts, np.float64).reshape(-1, 3)
@@ -376,7 +434,9 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     gains clean = dict(components=, largest=, verts_removed=, faces_removed=).
     evaluate: dict(gt_verts=, gt_faces=, d_max=, tau=, percentile=90, cell=0) -- the final mesh (the cleaned one with clean) is
     evaluated against the ground-truth mesh from where it lies on the device: the dict gains evaluation =
-    surface_eval()'s dict.  d_max and tau are required.
+    surface_eval()'s dict.  d_max and tau are required.  With register= (True or a dict, as surface_eval takes it) the final mesh
+    is, after the chain has returned, registered to the ground truth first and evaluation is that of the moved
+    vertices, with registration inside it; verts, faces and the PLY stay in the reconstruction's own frame.
     render: dict(cameras=[dict(R_rw, c_left, f, cx, cy), ...], w=, h=, z_min=, z_max=, step=0, min_weight=0, background=0,
     pgm_prefix=None) -- the integrated volume is ray cast from each camera at w x h (z_min and z_max are required):
     the dict gains renders = [dict(depth, normals, points, shaded, hits), ...]; with appearance each also carries grey and
@@ -503,6 +563,7 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     gt = None
     if evaluate is not None:
         ekw = dict(evaluate)
+        ereg = _register_request(ekw.pop("register", None), ekw.get("d_max"))  # applied to the final mesh, after the chain
         unknown = set(ekw) - set(EVALUATE_KEYS)
         if unknown:
             raise TypeError(f"unknown evaluate parameters {sorted(unknown)}")
@@ -826,6 +887,9 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             out["fill"] = dict(zip(capi.FILL_COUNTS, (int(v) for v in hcounts)))
         if gt is not None:
             out["evaluation"] = ev.asdict()
+            if ereg is not None:
+                out["evaluation"] = surface_eval(ctx, out["verts"], out["faces"], gv, gf, d_max=ekw.get("d_max"), tau=ekw.get("tau"),
+                                                 percentile=ekw.get("percentile", 90.0), cell=ekw.get("cell", 0.0), register=ereg)
         if rq is not None:
             out["renders"] = [dict(a, hits=int(routs[i].hits)) for i, a in enumerate(rarr)]
             if rkw.get("pgm_prefix"):

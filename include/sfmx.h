@@ -1223,6 +1223,97 @@ double sfmx_photo_last_resolve_us(const sfmx_photo* ph);
 /* the largest number of views the last successful run put into one batch (a property of the schedule, not of the result) */
 int sfmx_photo_last_batch(const sfmx_photo* ph);
 
+/* ---- registering a camera to the textured mesh: direct photometric alignment -------------------------------- */
+/* Inputs: a mesh, a sfmx_texture tx whose last successful run was on it, optionally a sfmx_level lv run on tx (then its atlas is
+ * read, as in the photometric error above), one picture I u8 [h][w], a camera (a sfmx_fusion_view under the z-buffer's camera
+ * rules, w and h the picture's) and the parameters.  Everything is IEEE double in the written order, nothing is contracted, and
+ * sqrt is taken on the host only.
+ *   render:     the key image of the whole mesh at cull = 0 for the current view, as sfmx_photo_run builds it
+ *   ok(x, y):   there is a winner f, f is front-facing and face_view[f] >= 0 (classes 3 and 4 above); outside the image: not ok
+ *   samples:    x = stride*i, y = stride*j with x < w, y < h;  nsx = ceil(w/stride), nsy = ceil(h/stride)
+ *   candidate:  ok(x', y') for every integer |x' - x| <= margin, |y' - y| <= margin
+ *   per candidate, with f, e_i, r_i, t_i, s of the photometric error at (x, y):
+ *     g   = that definition's g (the bilinear atlas read before its rounding)
+ *     z   = (double)|A_f| / s
+ *     r   = (double)I[y][x] - g;  used iff fabs(r) <= r_max (a NaN is not)
+ *     Gx  = 0.5*((double)I[y][x+1] - (double)I[y][x-1]);  Gy = 0.5*((double)I[y+1][x] - (double)I[y-1][x])
+ *     dx  = ((double)x - cx)/f;  dy = ((double)y - cy)/f;  q = (dx*z, dy*z, z);  iz = 1.0/z
+ *     a0  = (Gx*f)*iz;  a1 = (Gy*f)*iz;  a2 = -((a0*dx) + (a1*dy))
+ *     gw_b = (a0*R[0][b] + a1*R[1][b]) + a2*R[2][b]                  R = R_rw, its rows are the camera's axes
+ *     X_b  = c_b + ((R[0][b]*q0 + R[1][b]*q1) + R[2][b]*q2);  Q = X - pivot
+ *     J = (Q2*gw1 - Q1*gw2,  Q0*gw2 - Q2*gw0,  Q1*gw0 - Q0*gw1,  -gw0,  -gw1,  -gw2)
+ *   terms (28, the view alignment's order): A_mn = J_m*J_n for m <= n row by row (21), b_m = J_m*r (6), e = r*r (1); a sample
+ *     that is not used adds +0.0 to all 28; n = the used samples
+ *   ordered sum, solve, update, loop: the view alignment's, with p = pivot.  n < min_pixels: TOO_FEW.  A refused
+ *     Cholesky pivot, or a view with a non-finite entry after the update: DEGENERATE.  CONVERGED when, after the update,
+ *     |omega| <= eps_rot and |v| <= eps_trans.  TOO_FEW / DEGENERATE return the last view whose evaluation gave a step.
+ * The mesh is rendered again at every evaluation; the picture is read at integer positions only.  The gradient is the central
+ * difference (a forward difference shares the rounding error of I[y][x] with r and biases b), and margin >= 1 keeps its taps
+ * inside the image.  Sums, n and every iterate are bit-identical to the NumPy restatement in tests/palign_ref.py. */
+#define SFMX_PALIGN_ITERS_CAP 64 /* max_iters, and the length of the trace */
+#define SFMX_PALIGN_MARGIN_CAP 64
+enum { SFMX_PALIGN_CONVERGED = 0, SFMX_PALIGN_MAX_ITERS = 1, SFMX_PALIGN_TOO_FEW = 2, SFMX_PALIGN_DEGENERATE = 3 };
+typedef struct sfmx_palign sfmx_palign;  /* the model, the picture and the work buffers; they grow on demand and are kept */
+typedef struct sfmx_palign_params {
+  double z_min;     /* the z-buffer's; finite, > 0; no default */
+  double pivot[3];  /* the rotation's fixed point; finite; no default */
+  int max_iters;    /* evaluations at most, 1 .. 64 (default 10) */
+  int stride;       /* every stride-th pixel of every stride-th row is a sample, >= 1 (default 1) */
+  int margin;       /* a sample needs ok pixels this far around it, 1 .. 64 (default 4) */
+  int min_pixels;   /* fewer used samples than this end the loop with TOO_FEW, >= 1 (default 64) */
+  double r_max;     /* a candidate with |r| above this is not used; finite, >= 0 (default 255) */
+  double damping;   /* added to the diagonal of A, >= 0 (default 0) */
+  double eps_rot;   /* converged when |omega| <= eps_rot (default 5e-5) ... */
+  double eps_trans; /* ... and |v| <= eps_trans, a length in the mesh's units (default 1e-6) */
+} sfmx_palign_params;
+typedef struct sfmx_palign_result {
+  sfmx_fusion_view view; /* the refined view: R_rw and c_left move, the rest is the input's */
+  int status;            /* SFMX_PALIGN_CONVERGED, _MAX_ITERS, _TOO_FEW or _DEGENERATE */
+  int iterations;        /* evaluations made */
+  int32_t n[SFMX_PALIGN_ITERS_CAP];    /* per evaluation: samples used ... */
+  double e[SFMX_PALIGN_ITERS_CAP];     /* ... sum r^2 ... */
+  double rot[SFMX_PALIGN_ITERS_CAP];   /* ... |omega| of the step taken (0 when none was) ... */
+  double trans[SFMX_PALIGN_ITERS_CAP]; /* ... and |v| */
+} sfmx_palign_result;
+void sfmx_palign_default_params(sfmx_palign_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_palign_check_params(const sfmx_palign_params* p);
+int sfmx_palign_create(sfmx_ctx* ctx, sfmx_palign** out);
+void sfmx_palign_destroy(sfmx_ctx* ctx, sfmx_palign* pa);
+/* the model: tx (and lv, or NULL) are kept by reference and must outlive their use here, unchanged; verts double [n][3] and
+ * faces int32 [m][3] are copied into the object, from host pointers or (on_device = 1) device pointers.  SFMX_ERR_INVALID for a
+ * tx without a successful run, n or m other than that run's, an lv without a run or with another W or H, and a face index
+ * outside [0, n) (found on the device without any access through it); the model set before stays. */
+int sfmx_palign_set_model(sfmx_ctx* ctx, sfmx_palign* pa, const sfmx_texture* tx, const sfmx_level* lv, const double* verts, int n,
+                          const int32_t* faces, int m, int on_device);
+/* the same from a texture result on the host (sfmx_texture_read's arrays, the atlas tx's or a levelled one): face_view int32 [m],
+ * uv_half int32 [m][3][2], atlas u8 [H][W], all host pointers, copied; the object then refers to no texture object.  A textured
+ * face needs W, H >= 1; the atlas is read with the clamps of the definition whatever uv_half holds. */
+int sfmx_palign_set_model_arrays(sfmx_ctx* ctx, sfmx_palign* pa, const int32_t* face_view, const int32_t* uv_half, const uint8_t* atlas, int W,
+                                 int H, const double* verts, int n, const int32_t* faces, int m);
+/* the picture u8 [h][w], copied into the object from a host pointer or (on_device = 1) a device pointer; w <= 4096 and
+ * w h <= the z-buffer's limit */
+int sfmx_palign_set_image(sfmx_ctx* ctx, sfmx_palign* pa, const uint8_t* image, int w, int h, int on_device);
+/* one evaluation at the given view, no step: sums double [28] (A row by row upper, b, e) and *n.  SFMX_ERR_INVALID before a
+ * successful set_model and set_image, for a view whose w, h are not the picture's, that the z-buffer or sfmx_view_ok refuses,
+ * and for parameters outside their range; the object stays usable, and the model and picture stay set. */
+int sfmx_palign_system(sfmx_ctx* ctx, sfmx_palign* pa, const sfmx_fusion_view* view, const sfmx_palign_params* p, double* sums,
+                       int32_t* n);
+/* the Gauss-Newton loop from the given view.  The statuses are results: the call returns SFMX_OK with them.  A view that sees
+ * nothing is TOO_FEW. */
+int sfmx_palign_view(sfmx_ctx* ctx, sfmx_palign* pa, const sfmx_fusion_view* view, const sfmx_palign_params* p,
+                     sfmx_palign_result* out);
+/* the last evaluation, nsy x nsx values each: state u8 (0 not a candidate, 1 trimmed by r_max, 2 used) and r double (0.0 where
+ * the state is 0); either may be NULL.  SFMX_ERR_INVALID before a successful evaluation. */
+int sfmx_palign_read(sfmx_ctx* ctx, sfmx_palign* pa, uint8_t* state, double* r);
+/* nsx and nsy of the last evaluation; SFMX_ERR_INVALID (and zeros) before one */
+int sfmx_palign_sizes(const sfmx_palign* pa, int* nsx, int* nsy);
+/* device time (us) of the evaluations of the last call, of their z-buffers alone, and of k_pa_system with the tree's levels
+ * alone (the rest is the mask and its erosion), when timing is on (sfmx_set_timing), else 0 */
+double sfmx_palign_last_us(const sfmx_palign* pa);
+double sfmx_palign_last_zbuffer_us(const sfmx_palign* pa);
+double sfmx_palign_last_system_us(const sfmx_palign* pa);
+
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);
 int sfmx_debug_divsqrt(sfmx_ctx* ctx, const double* x, const double* y, int n, double* div_out,

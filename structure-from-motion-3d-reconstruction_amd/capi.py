@@ -80,6 +80,9 @@ SYMBOLS = [
     "sfmx_photo_add_view", "sfmx_photo_add_texture_views", "sfmx_photo_view_count", "sfmx_photo_set_batch", "sfmx_photo_run",
     "sfmx_photo_read", "sfmx_photo_sizes", "sfmx_photo_device_rendered", "sfmx_photo_last_us", "sfmx_photo_last_resolve_us",
     "sfmx_photo_last_batch",
+    "sfmx_palign_default_params", "sfmx_palign_check_params", "sfmx_palign_create", "sfmx_palign_destroy", "sfmx_palign_set_model",
+    "sfmx_palign_set_model_arrays", "sfmx_palign_set_image", "sfmx_palign_system", "sfmx_palign_view", "sfmx_palign_read", "sfmx_palign_sizes", "sfmx_palign_last_us",
+    "sfmx_palign_last_zbuffer_us", "sfmx_palign_last_system_us",
 ]
 
 
@@ -645,6 +648,53 @@ def align_check_params(**kw) -> bool:
     return load_library().sfmx_align_check_params(byref(align_params(**kw))) == SFMX_OK
 
 
+PALIGN_ITERS_CAP = 64  # SFMX_PALIGN_ITERS_CAP
+PALIGN_MARGIN_CAP = 64  # SFMX_PALIGN_MARGIN_CAP
+PALIGN_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")
+
+
+class PAlignParams(ctypes.Structure):
+    _fields_ = [("z_min", c_double), ("pivot", c_double * 3), ("max_iters", c_int), ("stride", c_int), ("margin", c_int),
+                ("min_pixels", c_int), ("r_max", c_double), ("damping", c_double), ("eps_rot", c_double), ("eps_trans", c_double)]
+
+
+class PAlignResult(ctypes.Structure):
+    _fields_ = AlignResult._fields_
+
+    asdict = AlignResult.asdict
+
+
+# z_min and pivot have no default (a depth and a point in the mesh's units)
+PALIGN_DEFAULTS = dict(max_iters=10, stride=1, margin=4, min_pixels=64, r_max=255.0, damping=0.0, eps_rot=5e-5, eps_trans=1e-6)
+
+
+def palign_params(z_min=0.0, pivot=(0.0, 0.0, 0.0), **kw) -> PAlignParams:
+    unknown = set(kw) - set(PALIGN_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown palign parameters {sorted(unknown)}")
+    d = {**PALIGN_DEFAULTS, **kw}
+    p = PAlignParams()
+    p.z_min = float(z_min)
+    p.pivot[:] = [float(v) for v in np.asarray(pivot, np.float64).reshape(3)]
+    for k in ("max_iters", "stride", "margin", "min_pixels"):
+        setattr(p, k, int(d[k]))
+    for k in ("r_max", "damping", "eps_rot", "eps_trans"):
+        setattr(p, k, float(d[k]))
+    return p
+
+
+def palign_default_params() -> dict:
+    """sfmx_palign_default_params as a dict (needs no device); z_min and pivot come back as zeros: they have no default"""
+    p = PAlignParams()
+    load_library().sfmx_palign_default_params(byref(p))
+    return {k: (tuple(p.pivot) if k == "pivot" else getattr(p, k)) for k, _ in PAlignParams._fields_}
+
+
+def palign_check_params(z_min=0.0, pivot=(0.0, 0.0, 0.0), **kw) -> bool:
+    """True if the sfmx_palign entries would accept the parameters; needs no device"""
+    return load_library().sfmx_palign_check_params(byref(palign_params(z_min, pivot, **kw))) == SFMX_OK
+
+
 REGISTER_ITERS_CAP = 64  # SFMX_REGISTER_ITERS_CAP
 REGISTER_TERMS = 37      # SFMX_REGISTER_TERMS
 REGISTER_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "DEGENERATE")
@@ -762,6 +812,9 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_level_last_bake_us.restype = c_double
         _lib.sfmx_photo_last_us.restype = c_double
         _lib.sfmx_photo_last_resolve_us.restype = c_double
+        _lib.sfmx_palign_last_us.restype = c_double
+        _lib.sfmx_palign_last_zbuffer_us.restype = c_double
+        _lib.sfmx_palign_last_system_us.restype = c_double
     return _lib
 
 
@@ -2242,6 +2295,128 @@ class Align:
             pass
 
 
+class PAlign:
+    """sfmx_palign: registration of a camera to the textured mesh by direct photometric Gauss-Newton alignment.
+    The model (a Texture's last run, optionally a Level's atlas, and the mesh) and one picture are set once and serve many
+    calls; the work buffers grow on demand and are kept."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_palign_create(ctx.h_, byref(self.h_)))
+        self.shape = None  # (h, w) of the picture
+        self._keep = None  # the Texture and Level the model refers to
+
+    def set_model(self, tx: "Texture", verts, faces, lv: "Level" = None, n=None, m=None):
+        """tx: the Texture whose last run was on this mesh; lv: a Level whose last run was on tx, or None.  verts float64 [n][3]
+        and faces int32 [m][3]: numpy arrays, or ints (device pointers) with n and m given; they are copied.  tx may also be a
+        texture result on the host, dict(face_view, uv_half, atlas) (lv then a level result dict(atlas) or None; host mesh)."""
+        if isinstance(tx, dict):
+            if isinstance(verts, int) or isinstance(faces, int):
+                raise TypeError("a texture result on the host goes with a host mesh")
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            fv = np.ascontiguousarray(tx["face_view"], np.int32).reshape(-1)
+            uvh = np.ascontiguousarray(tx["uv_half"], np.int32).reshape(-1, 3, 2)
+            atlas = np.ascontiguousarray((lv if lv is not None else tx)["atlas"], np.uint8)
+            if len(fv) != len(faces) or len(uvh) != len(faces) or atlas.ndim != 2:
+                raise SfmxError(SFMX_ERR_INVALID, "sfmx_palign: face_view and uv_half are per face, the atlas u8 [H][W]")
+            self.ctx._chk(self.ctx.lib.sfmx_palign_set_model_arrays(self.ctx.h_, self.h_, _p(fv, c_int32), _p(uvh, c_int32), _p(atlas, c_uint8),
+                                                                    c_int(atlas.shape[1]), c_int(atlas.shape[0]),
+                                                                    verts.ctypes.data_as(c_void_p), c_int(len(verts)),
+                                                                    faces.ctypes.data_as(c_void_p), c_int(len(faces))))
+            self._keep = None
+            return
+        on_dev = isinstance(verts, int)
+        if on_dev != isinstance(faces, int):
+            raise TypeError("verts and faces: both host arrays or both device pointers")
+        if on_dev:
+            pv, pf = c_void_p(verts), c_void_p(faces)
+            n, m = int(n), int(m)
+        else:
+            verts = _f64(verts).reshape(-1, 3)
+            faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+            n, m = len(verts), len(faces)
+            pv, pf = verts.ctypes.data_as(c_void_p), faces.ctypes.data_as(c_void_p)
+        self.ctx._chk(self.ctx.lib.sfmx_palign_set_model(self.ctx.h_, self.h_, tx.h_, lv.h_ if lv is not None else None, pv, c_int(n), pf,
+                                                         c_int(m), c_int(1 if on_dev else 0)))
+        self._keep = (tx, lv)
+
+    def set_image(self, image, shape=None):
+        """image: uint8 [h][w] numpy array, or an int (device pointer) with shape=(h, w); it is copied"""
+        if isinstance(image, int):
+            h, w = (int(v) for v in shape)
+            pi, on_dev = c_void_p(image), 1
+        else:
+            image = np.ascontiguousarray(image, np.uint8)
+            if image.ndim != 2:
+                raise TypeError("the picture is uint8 [h][w]")
+            h, w = image.shape
+            pi, on_dev = image.ctypes.data_as(c_void_p), 0
+        self.ctx._chk(self.ctx.lib.sfmx_palign_set_image(self.ctx.h_, self.h_, pi, c_int(w), c_int(h), c_int(on_dev)))
+        self.shape = (h, w)
+
+    def _view(self, cam: dict):
+        if self.shape is None:
+            raise SfmxError(SFMX_ERR_INVALID, "sfmx_palign: set_image first")
+        h, w = self.shape  # a camera that states another size is refused by the library
+        return fusion_view({**cam, "B": cam.get("B", 0.0)}, cam.get("w", w), cam.get("h", h))
+
+    def system(self, cam: dict, z_min=0.0, pivot=(0.0, 0.0, 0.0), **params):
+        """one evaluation at cam's pose, no step: (sums f64 [28] = A row by row upper, b, e; n).  cam: dict(R_rw, c_left, f, cx,
+        cy[, w, h]); z_min and pivot are required; params: PALIGN_DEFAULTS keys."""
+        p = palign_params(z_min, pivot, **params)
+        v = self._view(cam)
+        sums, n = np.zeros(28), c_int32(0)
+        self.ctx._chk(self.ctx.lib.sfmx_palign_system(self.ctx.h_, self.h_, byref(v), byref(p), _p(sums, c_double), byref(n)))
+        return sums, int(n.value)
+
+    def view(self, cam: dict, z_min=0.0, pivot=(0.0, 0.0, 0.0), **params) -> dict:
+        """the Gauss-Newton loop from cam's pose: dict(view, status, iterations, trace=[(n, e, |omega|, |v|), ...])"""
+        p = palign_params(z_min, pivot, **params)
+        v = self._view(cam)
+        out = PAlignResult()
+        self.ctx._chk(self.ctx.lib.sfmx_palign_view(self.ctx.h_, self.h_, byref(v), byref(p), byref(out)))
+        return out.asdict()
+
+    def sizes(self):
+        """(nsy, nsx) of the last evaluation; raises before one"""
+        nsx, nsy = c_int(0), c_int(0)
+        rc = self.ctx.lib.sfmx_palign_sizes(self.h_, byref(nsx), byref(nsy))
+        if rc != SFMX_OK:
+            raise SfmxError(rc, "sfmx_palign_sizes: no evaluation")
+        return nsy.value, nsx.value
+
+    def read(self):
+        """(state u8 [nsy][nsx]: 0 not a candidate, 1 trimmed by r_max, 2 used; r f64 [nsy][nsx]) of the last evaluation"""
+        nsy, nsx = self.sizes()
+        state, r = np.zeros((nsy, nsx), np.uint8), np.zeros((nsy, nsx))
+        self.ctx._chk(self.ctx.lib.sfmx_palign_read(self.ctx.h_, self.h_, _p(state, c_uint8), _p(r, c_double)))
+        return state, r
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_palign_last_us(self.h_))
+
+    def last_zbuffer_us(self) -> float:
+        return float(self.ctx.lib.sfmx_palign_last_zbuffer_us(self.h_))
+
+    def last_system_us(self) -> float:
+        """k_pa_system and the tree's levels alone; last_us - last_zbuffer_us - this is the mask and its erosion"""
+        return float(self.ctx.lib.sfmx_palign_last_system_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_palign_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Register:
     """sfmx_register: Sim(3) point-to-plane registration of source points to a target mesh.  One target serves
     many sources; the target's grid and the work buffers are kept between calls."""
@@ -2711,6 +2886,9 @@ class Context:
 
     def photo(self) -> "Photo":
         return Photo(self)
+
+    def palign(self) -> "PAlign":
+        return PAlign(self)
 
     def stereo(self, w: int, h: int, **params) -> Stereo:
         return Stereo(self, w, h, **params)

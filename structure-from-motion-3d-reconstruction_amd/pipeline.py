@@ -260,6 +260,7 @@ class AlignRequest(ctypes.Structure):
 
 
 PHOTO_KEYS = ("background", "pgm_prefix")
+PALIGN_KEYS = ("cameras", "images", "levels", "z_min", "pivot") + tuple(capi.PALIGN_DEFAULTS)
 
 
 class PhotoRequest(ctypes.Structure):
@@ -375,6 +376,85 @@ def surface_register(ctx: capi.Context, verts, faces, gt_verts, gt_faces, d_max=
     return res
 
 
+def reduce_image(image) -> np.ndarray:
+    """one level of view_register's pyramid: (a + b + c + d + 2) >> 2 over 2 x 2 blocks of a u8 picture; an odd trailing row or
+    column is dropped"""
+    I = np.ascontiguousarray(image, np.uint8)
+    h, w = I.shape[0] // 2, I.shape[1] // 2
+    q = I[:2 * h, :2 * w].astype(np.int64)
+    return ((q[0::2, 0::2] + q[0::2, 1::2] + q[1::2, 0::2] + q[1::2, 1::2] + 2) >> 2).astype(np.uint8)
+
+
+def reduce_camera(cam: dict) -> dict:
+    """the camera of reduce_image's picture: f / 2, (cx - 0.5) / 2, (cy - 0.5) / 2, w // 2, h // 2 (pixel i of the reduced picture
+    is centred at 2 i + 0.5 of the full one)"""
+    out = dict(cam)
+    out.update(f=float(cam["f"]) / 2.0, cx=(float(cam["cx"]) - 0.5) / 2.0, cy=(float(cam["cy"]) - 0.5) / 2.0, w=int(cam["w"]) // 2,
+               h=int(cam["h"]) // 2)
+    return out
+
+
+def view_register(ctx: capi.Context, tx: "capi.Texture", verts, faces, cam: dict, image, z_min=None, lv: "capi.Level" = None, levels=1,
+                  init=None, pivot=None, **params) -> dict:
+    """Registers a camera to the textured mesh by direct photometric Gauss-Newton alignment on the device (DESIGN.md 29;
+    capi.PAlign).  tx: the Texture whose last run was on (verts, faces); lv: a Level run on tx, then its atlas is read (or both
+    as results on the host: dict(face_view, uv_half, atlas) and dict(atlas), as fuse returns them).  cam:
+    dict(R_rw, c_left, f, cx, cy) of the picture `image` u8 [h][w] at a rough pose; init: dict(R_rw, c_left) replaces cam's pose
+    as the start.  z_min (required) is the z-buffer's.  pivot defaults to the centre of the bounding box of the vertices a face
+    uses, eps_trans to 1e-5 x that box's diagonal.  levels > 1 runs coarse to fine on the host: level l uses the picture reduced l
+    times (reduce_image) under the camera reduced as often (reduce_camera), starts at the view the coarser level returned and
+    keeps margin in pixels.  params: capi.PALIGN_DEFAULTS keys.
+    Returns dict(view, status, iterations (over all levels), n and rms = sqrt(e / n) of the last evaluation (rms nan when n = 0),
+    levels = [dict(view, status, iterations, trace) per level, coarsest first])."""
+    if z_min is None:
+        raise TypeError("view registration needs z_min (a depth in the mesh's units; there is no default)")
+    unknown = set(params) - set(capi.PALIGN_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown palign parameters {sorted(unknown)}")
+    levels = int(levels)
+    if levels < 1:
+        raise ValueError("levels >= 1")
+    rv = np.ascontiguousarray(verts, np.float64).reshape(-1, 3)
+    rf = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    if len(rf) and (rf.min() < 0 or rf.max() >= len(rv)):
+        raise ValueError("a face index is outside the vertices")
+    if pivot is None or "eps_trans" not in params:
+        if not len(rf):
+            raise ValueError("a mesh without faces has no bounding box: give pivot and eps_trans")
+        used = rv[np.unique(rf.ravel())]
+        lo, hi = used.min(0), used.max(0)
+        if pivot is None:
+            pivot = [float(lo[a]) + 0.5 * (float(hi[a]) - float(lo[a])) for a in range(3)]
+        if "eps_trans" not in params:
+            params["eps_trans"] = 1e-5 * float(np.sqrt(sum((float(hi[a]) - float(lo[a])) ** 2 for a in range(3))))
+    img = np.ascontiguousarray(image, np.uint8)
+    if img.ndim != 2:
+        raise TypeError("the picture is uint8 [h][w]")
+    cams, imgs = [dict(cam, w=img.shape[1], h=img.shape[0])], [img]
+    if init is not None:
+        cams[0].update(R_rw=init["R_rw"], c_left=init["c_left"])
+    for _ in range(1, levels):
+        imgs.append(reduce_image(imgs[-1]))
+        cams.append(reduce_camera(cams[-1]))
+        if min(imgs[-1].shape) < 1:
+            raise ValueError("the picture is too small for that many levels")
+    pa = ctx.palign()
+    try:
+        pa.set_model(tx, rv, rf, lv=lv)
+        view, per = cams[0], []
+        for l in range(levels - 1, -1, -1):
+            pa.set_image(imgs[l])
+            res = pa.view(dict(cams[l], R_rw=view["R_rw"], c_left=view["c_left"]), z_min, pivot, **params)
+            per.append(res)
+            view = res["view"]
+    finally:
+        pa.close()
+    last = per[-1]
+    n, e = last["trace"][-1][0], last["trace"][-1][1]
+    return dict(view=last["view"], status=last["status"], iterations=sum(r["iterations"] for r in per), n=n,
+                rms=float(np.sqrt(e / n)) if n > 0 else float("nan"), levels=per)
+
+
 def surface_eval(ctx: capi.Context, verts, faces, gt_verts, gt_faces, d_max=None, tau=None, percentile=90.0, cell=0.0,
                  register=None) -> dict:
     """Accuracy and completeness of the reconstruction (verts, faces) against the ground truth (gt_verts, gt_faces), sampled at
@@ -416,7 +496,7 @@ def _split_fusion_params(params: dict):
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
          consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, fill=False, raster=None,
-         visibility=False, texture=False, level=False, photo=False, **params) -> dict:
+         visibility=False, texture=False, level=False, photo=False, palign=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -491,7 +571,12 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     own views on the device (z_min is the texture's), from the levelled atlas with level, and compared with their
     images.  The dict gains photo = dict(rendered u8 / cls u8 / face i32 [V][h][w], classes i64 [V][5], stats i64 [V][2][3], hist
     i64 [V][2][256], summary = capi.photo_summary's dict).  pgm_prefix writes <prefix>_<q>_photo.pgm.  Everything else is what it
-    is without photo."""
+    is without photo.
+    palign: dict(cameras=[dict(R_rw, c_left, f, cx, cy), ...], images=[u8 [h][w], ...], levels=1, z_min=the texture's, pivot=None,
+    capi.PALIGN_DEFAULTS keys) (needs texture) -- after the chain has returned, each listed camera is registered to the final
+    textured mesh by direct photometric alignment on the device (view_register, on the levelled atlas with level).
+    The dict gains palign = [view_register's dict per camera] ([] for a mesh without faces).  Everything else is what it is
+    without palign."""
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -666,6 +751,22 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
             raise TypeError("photo needs texture")
         photo_prefix = pkw.pop("pgm_prefix", None)
         pq = PhotoRequest(capi.photo_params(xq.params.z_min, **pkw))  # the texture's z_min
+    gq = None
+    if palign:
+        if not isinstance(palign, dict):
+            raise TypeError("palign is a dict with cameras and images")
+        gq = dict(palign)
+        unknown = set(gq) - set(PALIGN_KEYS)
+        if unknown:
+            raise TypeError(f"unknown palign parameters {sorted(unknown)}")
+        if xq is None:
+            raise TypeError("palign needs texture")
+        if "cameras" not in gq or "images" not in gq or len(gq["cameras"]) != len(gq["images"]):
+            raise TypeError("palign needs cameras and images, one picture per camera")
+        gcams, gimgs = list(gq.pop("cameras")), list(gq.pop("images"))
+        glevels, gz, gpivot = int(gq.pop("levels", 1)), float(gq.pop("z_min", xq.params.z_min)), gq.pop("pivot", None)
+        if glevels < 1 or not capi.palign_check_params(gz, (0.0, 0.0, 0.0) if gpivot is None else gpivot, **gq):
+            raise ValueError("palign parameters outside their range")
     aq = None
     if align:
         gkw = {} if align is True else dict(align)
@@ -874,6 +975,9 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                 out["level"] = lev
             if obj_path:
                 write_textured_obj(obj_path, out["verts"], out["faces"], tex["uv"], lev["atlas"] if lq is not None else tex["atlas"])
+        if gq is not None:  # in Python, after the chain: the host library knows nothing of it
+            out["palign"] = [view_register(ctx, tex, out["verts"], out["faces"], c, im, z_min=gz, lv=lev if lq is not None else None,
+                                           levels=glevels, pivot=gpivot, **gq) for c, im in zip(gcams, gimgs)] if len(out["faces"]) else []
         if cp is not None:
             done = counts[:len(pr)][counts[:len(pr), 0] >= 0]
             out["consistency"] = dict(valid=[int(v) for v in done[:, 0]], kept=[int(v) for v in done[:, 1]])
@@ -971,7 +1075,7 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     pair's view to the volume before it enters it; 'simplify' (True or a dict, as fuse) simplifies the final surface by exact vertex
     clustering; 'smooth' (True or a dict, as fuse) smooths it with the exact Taubin filter first; 'fill' (True or a dict, as fuse) fills its small
     holes before that; 'raster' (a dict, as fuse) renders the final mesh from further cameras; 'visibility' (a dict, as fuse) first removes
-    the faces no pair's camera sees from the front; 'texture' (a dict, as fuse) bakes a texture atlas for the final mesh; 'level' (True or a dict, as fuse, with texture) levels its seams; 'photo' (True or a dict, as fuse, with texture) renders the textured mesh back into the texture's views and measures the photometric error.  The run itself, its log and every other output are unchanged.
+    the faces no pair's camera sees from the front; 'texture' (a dict, as fuse) bakes a texture atlas for the final mesh; 'level' (True or a dict, as fuse, with texture) levels its seams; 'photo' (True or a dict, as fuse, with texture) renders the textured mesh back into the texture's views and measures the photometric error; 'palign' (a dict, as fuse, with texture) registers further cameras to the textured mesh.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -1046,10 +1150,11 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         texture = fz.pop("texture", False)
         level = fz.pop("level", False)
         photo = fz.pop("photo", False)
+        palign = fz.pop("palign", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
                                  appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align,
                                  simplify=simplify, smooth=smooth, fill=fill, raster=raster, visibility=visibility, texture=texture,
-                                 level=level, photo=photo, **fz)
+                                 level=level, photo=photo, palign=palign, **fz)
     return out
 
 

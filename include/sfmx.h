@@ -277,6 +277,12 @@ void sfmx_stereo_destroy(sfmx_ctx* ctx, sfmx_stereo* st);
  * rect_out (optional): u8 [2][h][w] rectified images.  sum_out (optional): u16 [h][w][D] aggregated cost S. */
 int sfmx_stereo_disparity(sfmx_ctx* ctx, sfmx_stereo* st, const uint8_t* img_l, const uint8_t* img_r, int on_device,
                           const double* H_l, const double* H_r, int16_t* disp16_out, uint8_t* rect_out, uint16_t* sum_out);
+/* the rectification alone: both rectified images are left on the device inside st (for the _add_stereo_view entries that take
+ * the left rectified image); the disparity map inside st no longer belongs to these images, and until the next
+ * sfmx_stereo_disparity every entry that takes st's map (sfmx_fusion / _shade / _consist _add_stereo_view, sfmx_align_stereo_view)
+ * returns SFMX_ERR_INVALID */
+int sfmx_stereo_rectify(sfmx_ctx* ctx, sfmx_stereo* st, const uint8_t* img_l, const uint8_t* img_r, int on_device, const double* H_l,
+                        const double* H_r);
 /* device time (us) of the kernels of the last sfmx_stereo_disparity call when timing is on (sfmx_set_timing), else 0 */
 double sfmx_stereo_last_us(const sfmx_stereo* st);
 
@@ -1313,6 +1319,76 @@ int sfmx_palign_sizes(const sfmx_palign* pa, int* nsx, int* nsy);
 double sfmx_palign_last_us(const sfmx_palign* pa);
 double sfmx_palign_last_zbuffer_us(const sfmx_palign* pa);
 double sfmx_palign_last_system_us(const sfmx_palign* pa);
+
+/* ---- shape from silhouette: the visual hull on the fusion grid, and carving a volume with it --------------- */
+/* A carve object keeps an ordered list of views: a sfmx_fusion_view (B is unused, f > 0) and the signed squared distance map of
+ * its silhouette.  For a picture I u8 [h][w] and a threshold, m = I >= threshold is the inside class, D2 the squared distance to
+ * the nearest pixel OF THE IMAGE of the other class, capped at cap * cap, and sd2 = m ? -D2 : +D2 (int16, never 0): the exact
+ * truncated Euclidean distance transform.  sfmx_carve_run gives every grid point of a volume the largest, over the views that
+ * see it, of clamp((d * q2) / (f * trunc), -1, 1) with d = +-(sqrt(|sd2|) - 0.5) pixels at the point's nearest pixel and q2 its
+ * depth: negative inside every silhouette, positive where some camera sees the point outside its own (the sign convention of
+ * DESIGN.md 13).  The maps are integers and the views are combined by max, so maps, hull, view counts, the carved volume and the
+ * counters are bit-identical to the NumPy restatement in tests/carve_ref.py whatever the batching or the order of the views. */
+typedef struct sfmx_carve sfmx_carve;  /* retained views (camera and sd2 map) and the hull of the last run, on the device */
+enum { SFMX_CARVE_INTERSECT = 0, SFMX_CARVE_CLEAR = 1 };
+typedef struct sfmx_carve_params {
+  int cap;        /* the distance maps' cap in pixels, 1 .. 64 (default 16); the run's must be the one its views were built with */
+  int min_views;  /* a grid point's hull value is defined when at least this many views see it; >= 1 (default 1) */
+  double margin;  /* sfmx_carve_apply carves where hull > margin; finite, >= 0, < 1 (default 0.5) */
+  int mode;       /* sfmx_carve_apply: SFMX_CARVE_INTERSECT (default) or SFMX_CARVE_CLEAR */
+  double trunc;   /* the length a hull value of 1 stands for, >= 0 (default 0 = 4 * voxel, as the fusion resolves it) */
+} sfmx_carve_params;
+/* the grid of a run: point (i, j, k) at origin + (i, j, k) * voxel, with sfmx_fusion_params' limits */
+typedef struct sfmx_carve_volume {
+  double origin[3];
+  double voxel;
+  int nx, ny, nz;
+} sfmx_carve_volume;
+void sfmx_carve_default_params(sfmx_carve_params* p);
+/* SFMX_OK or SFMX_ERR_INVALID; needs no device */
+int sfmx_carve_check_params(const sfmx_carve_params* p);
+int sfmx_carve_create(sfmx_ctx* ctx, sfmx_carve** out);
+void sfmx_carve_destroy(sfmx_ctx* ctx, sfmx_carve* cv);
+/* drop every view and the result (the device memory is kept for the next ones) */
+int sfmx_carve_reset(sfmx_ctx* ctx, sfmx_carve* cv);
+/* append a view: image u8 [h][w], a host pointer or (on_device = 1) a device pointer; its sd2 map at threshold (1 .. 255) and
+ * cap (1 .. 64) is built and kept (2 bytes per pixel), the picture is not.  Views of different sizes may be mixed (w <= 4096,
+ * w * h < 2^30, as every stage's views).  SFMX_ERR_INVALID for f <= 0 and for anything the other stages' views refuse. */
+int sfmx_carve_add_view(sfmx_ctx* ctx, sfmx_carve* cv, const sfmx_fusion_view* view, const uint8_t* image, int on_device, int threshold,
+                        int cap);
+/* the same with the left rectified image of st's last sfmx_stereo_disparity / sfmx_stereo_rectify call, from where it lies on
+ * the device (a rectified picture is 0 where its source has no pixel) */
+int sfmx_carve_add_stereo_view(sfmx_ctx* ctx, sfmx_carve* cv, const sfmx_fusion_view* view, const sfmx_stereo* st, int threshold, int cap);
+int sfmx_carve_view_count(const sfmx_carve* cv);
+/* out int32 [view count]: the pixels of each view's inside class (counted on the device when the view was added) */
+int sfmx_carve_inside_pixels(const sfmx_carve* cv, int32_t* out);
+/* view i's map to the host: sd2_out int16 [h][w] */
+int sfmx_carve_read_view(sfmx_ctx* ctx, sfmx_carve* cv, int i, int16_t* sd2_out);
+/* views per launch of the hull kernel, 1 .. 4096; 0 (default) = automatic.  Changes the speed only. */
+int sfmx_carve_set_batch(sfmx_carve* cv, int k);
+/* the hull of every view on vol.  SFMX_ERR_INVALID without a view, with a view built at another cap, a volume outside the
+ * fusion's limits or parameters outside their range; a failed run leaves no result. */
+int sfmx_carve_run(sfmx_ctx* ctx, sfmx_carve* cv, const sfmx_carve_volume* vol, const sfmx_carve_params* p);
+/* the last run to the host: hull double / views int32 [nz][ny][nx] (the views that saw the point; hull is -1 where none did);
+ * either may be NULL.  SFMX_ERR_INVALID before a successful run. */
+int sfmx_carve_read(sfmx_ctx* ctx, sfmx_carve* cv, double* hull, int32_t* views);
+/* carve fu's volume (its pending views are integrated first) with the last run, whose grid must be fu's.  With
+ * W = max(1, fu's min_weight), at every defined point with hull > margin, hm = hull - margin: CLEAR makes the point undefined
+ * (count 0, sum +0); INTERSECT gives an undefined point, or a point whose value sum / count is below hm, the value hm (count
+ * W, sum hm * W).  Every other point keeps its bits.  counts int32 [3] (or NULL): the defined points, those outside (hull >
+ * margin) and those whose sum or count changed.  Of p only margin and mode are read.  A refused call (no run, another grid, bad parameters)
+ * leaves fu as it was: its pending views stay pending and its cached surface stays. */
+int sfmx_carve_apply(sfmx_ctx* ctx, sfmx_carve* cv, sfmx_fusion* fu, const sfmx_carve_params* p, int32_t* counts);
+/* counts int32 [3]: the defined points and those outside (hull > p->margin) of the last run, from the hull alone, and 0: what
+ * sfmx_carve_apply would return as its first two counters, without a fusion object */
+int sfmx_carve_count(sfmx_ctx* ctx, sfmx_carve* cv, const sfmx_carve_params* p, int32_t* counts);
+/* write the last run into fu (same grid; pending views are integrated first, then every point is overwritten): count W and sum
+ * hull * W where defined, count 0 and sum +0 elsewhere.  The extraction and every stage behind it then work on the hull. */
+int sfmx_carve_store(sfmx_ctx* ctx, sfmx_carve* cv, sfmx_fusion* fu);
+/* device time (us) of the kernels of the last sfmx_carve_run / _apply / _store, and of the two distance transform kernels of
+ * the last sfmx_carve_add_view, when timing is on (sfmx_set_timing), else 0 */
+double sfmx_carve_last_us(const sfmx_carve* cv);
+double sfmx_carve_last_edt_us(const sfmx_carve* cv);
 
 /* ---- self-check hooks used by the parity tests (device arithmetic vs the host libm) ---------- */
 int sfmx_debug_hypot(sfmx_ctx* ctx, const double* x, const double* y, int n, double* out);

@@ -31,7 +31,7 @@ SYMBOLS = [
     "sfmx_comm_allreduce_f64", "sfmx_comm_allreduce_u64_max",
     "sfmx_debug_hypot", "sfmx_debug_divsqrt", "sfmx_debug_klt_slow_steps",
     "sfmx_stereo_default_params", "sfmx_stereo_check_params", "sfmx_stereo_create", "sfmx_stereo_destroy", "sfmx_stereo_disparity",
-    "sfmx_stereo_last_us",
+    "sfmx_stereo_rectify", "sfmx_stereo_last_us",
     "sfmx_fusion_default_params", "sfmx_fusion_check_params", "sfmx_fusion_create", "sfmx_fusion_destroy", "sfmx_fusion_reset",
     "sfmx_fusion_add_view", "sfmx_fusion_add_stereo_view", "sfmx_fusion_integrate", "sfmx_fusion_read", "sfmx_fusion_extract",
     "sfmx_fusion_last_us",
@@ -83,6 +83,9 @@ SYMBOLS = [
     "sfmx_palign_default_params", "sfmx_palign_check_params", "sfmx_palign_create", "sfmx_palign_destroy", "sfmx_palign_set_model",
     "sfmx_palign_set_model_arrays", "sfmx_palign_set_image", "sfmx_palign_system", "sfmx_palign_view", "sfmx_palign_read", "sfmx_palign_sizes", "sfmx_palign_last_us",
     "sfmx_palign_last_zbuffer_us", "sfmx_palign_last_system_us",
+    "sfmx_carve_default_params", "sfmx_carve_check_params", "sfmx_carve_create", "sfmx_carve_destroy", "sfmx_carve_reset",
+    "sfmx_carve_add_view", "sfmx_carve_add_stereo_view", "sfmx_carve_inside_pixels", "sfmx_carve_view_count", "sfmx_carve_read_view", "sfmx_carve_set_batch", "sfmx_carve_run", "sfmx_carve_read",
+    "sfmx_carve_apply", "sfmx_carve_count", "sfmx_carve_store", "sfmx_carve_last_us", "sfmx_carve_last_edt_us",
 ]
 
 
@@ -214,6 +217,47 @@ def consist_default_params() -> dict:
 def consist_check_params(**kw) -> bool:
     """True if sfmx_consist_filter would accept the parameters; needs no device"""
     return load_library().sfmx_consist_check_params(byref(consist_params(**kw))) == SFMX_OK
+
+
+class CarveParams(ctypes.Structure):
+    _fields_ = [("cap", c_int), ("min_views", c_int), ("margin", c_double), ("mode", c_int), ("trunc", c_double)]
+
+
+class CarveVolume(ctypes.Structure):
+    _fields_ = [("origin", c_double * 3), ("voxel", c_double), ("nx", c_int), ("ny", c_int), ("nz", c_int)]
+
+
+CARVE_MODES = ("intersect", "clear")
+CARVE_COUNTS = ("defined", "outside", "changed")
+CARVE_DEFAULTS = dict(cap=16, min_views=1, margin=0.5, mode="intersect", trunc=0.0)
+
+
+def carve_params(**kw) -> CarveParams:
+    unknown = set(kw) - set(CARVE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown carve parameters {sorted(unknown)}")
+    kw = {**CARVE_DEFAULTS, **kw}
+    for k in ("cap", "min_views"):
+        if isinstance(kw[k], (bool, np.bool_)) or not isinstance(kw[k], (int, np.integer)):
+            raise TypeError(f"carve {k} is an int")
+    mode = kw["mode"]
+    if isinstance(mode, str):
+        if mode not in CARVE_MODES:
+            raise ValueError(f"carve mode is one of {CARVE_MODES}")
+        mode = CARVE_MODES.index(mode)
+    return CarveParams(int(kw["cap"]), int(kw["min_views"]), float(kw["margin"]), int(mode), float(kw["trunc"]))
+
+
+def carve_default_params() -> dict:
+    """sfmx_carve_default_params as a dict (needs no device)"""
+    p = CarveParams()
+    load_library().sfmx_carve_default_params(byref(p))
+    return dict(cap=p.cap, min_views=p.min_views, margin=p.margin, mode=CARVE_MODES[p.mode], trunc=p.trunc)
+
+
+def carve_check_params(**kw) -> bool:
+    """True if the sfmx_carve entries would accept the parameters; needs no device"""
+    return load_library().sfmx_carve_check_params(byref(carve_params(**kw))) == SFMX_OK
 
 
 class CleanParams(ctypes.Structure):
@@ -815,6 +859,8 @@ def load_library() -> ctypes.CDLL:
         _lib.sfmx_palign_last_us.restype = c_double
         _lib.sfmx_palign_last_zbuffer_us.restype = c_double
         _lib.sfmx_palign_last_system_us.restype = c_double
+        _lib.sfmx_carve_last_us.restype = c_double
+        _lib.sfmx_carve_last_edt_us.restype = c_double
     return _lib
 
 
@@ -1019,6 +1065,119 @@ class Shade:
     def close(self):
         if self.h_:
             self.ctx.lib.sfmx_shade_destroy(self.ctx.h_, self.h_)
+            self.h_ = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Carve:
+    """sfmx_carve: retained views (camera, signed squared distance map of the silhouette) on the device, their visual hull on a
+    volume, and carving a Fusion with it."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.shapes = []
+        self.dims = None
+        self.h_ = c_void_p()
+        ctx._chk(ctx.lib.sfmx_carve_create(ctx.h_, byref(self.h_)))
+
+    def add_view(self, cam: dict, image, shape=None, threshold=1, cap=16):
+        """image: u8 [h][w] numpy array (a picture or a mask), or an int (device pointer) with shape=(h, w); cam needs no B"""
+        if isinstance(image, int):
+            h, w = shape
+            ptr, on_dev = c_void_p(image), 1
+        else:
+            image = np.ascontiguousarray(image, np.uint8)
+            h, w = image.shape
+            ptr, on_dev = image.ctypes.data_as(c_void_p), 0
+        v = fusion_view({**cam, "B": cam.get("B", 0.0)}, w, h)
+        self.ctx._chk(self.ctx.lib.sfmx_carve_add_view(self.ctx.h_, self.h_, byref(v), ptr, c_int(on_dev), c_int(int(threshold)),
+                                                       c_int(int(cap))))
+        self.shapes.append((int(h), int(w)))
+
+    def add_stereo_view(self, cam: dict, st: "Stereo", threshold=1, cap=16):
+        """the left rectified image st computed last, from where it lies on the device"""
+        v = fusion_view({**cam, "B": cam.get("B", 0.0)}, st.w, st.h)
+        self.ctx._chk(self.ctx.lib.sfmx_carve_add_stereo_view(self.ctx.h_, self.h_, byref(v), st.h_, c_int(int(threshold)), c_int(int(cap))))
+        self.shapes.append((int(st.h), int(st.w)))
+
+    def view_count(self) -> int:
+        return int(self.ctx.lib.sfmx_carve_view_count(self.h_))
+
+    def inside_pixels(self) -> list:
+        """per view, the pixels of the inside class"""
+        n = self.view_count()
+        out = np.zeros(max(n, 1), np.int32)
+        if self.ctx.lib.sfmx_carve_inside_pixels(self.h_, _p(out, c_int32)) != SFMX_OK:
+            raise SfmxError(SFMX_ERR_INVALID, "sfmx_carve_inside_pixels")
+        return [int(v) for v in out[:n]]
+
+    def reset(self):
+        self.ctx._chk(self.ctx.lib.sfmx_carve_reset(self.ctx.h_, self.h_))
+        self.shapes = []
+        self.dims = None
+
+    def read_view(self, i: int) -> np.ndarray:
+        """sd2 int16 [h][w] of view i"""
+        h, w = self.shapes[i] if 0 <= i < len(self.shapes) else (1, 1)
+        sd2 = np.zeros((h, w), np.int16)
+        self.ctx._chk(self.ctx.lib.sfmx_carve_read_view(self.ctx.h_, self.h_, c_int(i), sd2.ctypes.data_as(c_void_p)))
+        return sd2
+
+    def set_batch(self, k: int):
+        """views per launch of the hull kernel (0 = automatic); changes the speed only"""
+        if self.ctx.lib.sfmx_carve_set_batch(self.h_, c_int(int(k))) != SFMX_OK:
+            raise SfmxError(SFMX_ERR_INVALID, "carve batch outside 0 .. 4096")
+
+    def run(self, origin, voxel, dims, **params):
+        """the hull of every view on the volume; params: CARVE_DEFAULTS keys"""
+        p = carve_params(**params)
+        vol = CarveVolume()
+        vol.origin[:] = [float(v) for v in origin]
+        vol.voxel = float(voxel)
+        vol.nx, vol.ny, vol.nz = (int(v) for v in dims)
+        self.dims = None
+        self.ctx._chk(self.ctx.lib.sfmx_carve_run(self.ctx.h_, self.h_, byref(vol), byref(p)))
+        self.dims = (vol.nx, vol.ny, vol.nz)
+
+    def read(self):
+        """(hull float64, views int32), both [nz][ny][nx], of the last run"""
+        nx, ny, nz = self.dims if self.dims else (1, 1, 1)
+        hull, views = np.zeros((nz, ny, nx)), np.zeros((nz, ny, nx), np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_carve_read(self.ctx.h_, self.h_, _p(hull, c_double), _p(views, c_int32)))
+        return hull, views
+
+    def apply(self, fu: "Fusion", **params) -> dict:
+        """carve fu's volume with the last run; params: CARVE_DEFAULTS keys (margin and mode are read).  dict of CARVE_COUNTS"""
+        p = carve_params(**params)
+        counts = np.zeros(3, np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_carve_apply(self.ctx.h_, self.h_, fu.h_, byref(p), _p(counts, c_int32)))
+        return dict(zip(CARVE_COUNTS, (int(c) for c in counts)))
+
+    def count(self, **params) -> dict:
+        """dict of CARVE_COUNTS of the last run from the hull alone (margin is read; changed is 0): apply()'s first two counters"""
+        p = carve_params(**params)
+        counts = np.zeros(3, np.int32)
+        self.ctx._chk(self.ctx.lib.sfmx_carve_count(self.ctx.h_, self.h_, byref(p), _p(counts, c_int32)))
+        return dict(zip(CARVE_COUNTS, (int(c) for c in counts)))
+
+    def store(self, fu: "Fusion"):
+        """write the last run into fu: the extraction and every stage behind it then work on the hull"""
+        self.ctx._chk(self.ctx.lib.sfmx_carve_store(self.ctx.h_, self.h_, fu.h_))
+
+    def last_us(self) -> float:
+        return float(self.ctx.lib.sfmx_carve_last_us(self.h_))
+
+    def last_edt_us(self) -> float:
+        return float(self.ctx.lib.sfmx_carve_last_edt_us(self.h_))
+
+    def close(self):
+        if self.h_:
+            self.ctx.lib.sfmx_carve_destroy(self.ctx.h_, self.h_)
             self.h_ = c_void_p()
 
     def __del__(self):
@@ -2524,6 +2683,23 @@ class Stereo:
         self.h_ = c_void_p()
         ctx._chk(ctx.lib.sfmx_stereo_create(ctx.h_, c_int(w), c_int(h), byref(self.params), byref(self.h_)))
 
+    def rectify(self, img_l, img_r, H_l, H_r):
+        """the rectification alone (no disparity): both rectified images stay on the device for the add_stereo_view entries that
+        take the left one.  img_l / img_r as disparity() takes them."""
+        on_dev = isinstance(img_l, int)
+        if on_dev != isinstance(img_r, int):
+            raise TypeError("img_l and img_r: both host arrays or both device pointers")
+        if on_dev:
+            pl, pr = c_void_p(img_l), c_void_p(img_r)
+        else:
+            img_l = np.ascontiguousarray(img_l, np.uint8)
+            img_r = np.ascontiguousarray(img_r, np.uint8)
+            assert img_l.shape == (self.h, self.w) and img_r.shape == (self.h, self.w)
+            pl, pr = _p(img_l, c_uint8), _p(img_r, c_uint8)
+        Hl, Hr = _f64(H_l).reshape(9), _f64(H_r).reshape(9)
+        self.ctx._chk(self.ctx.lib.sfmx_stereo_rectify(self.ctx.h_, self.h_, pl, pr, c_int(1 if on_dev else 0), _p(Hl, c_double),
+                                                       _p(Hr, c_double)))
+
     def disparity(self, img_l, img_r, H_l, H_r, want_rect: bool = False, want_sum: bool = False):
         """img_l / img_r: u8 [h][w] numpy arrays, or ints (device pointers of u8 [h][w] in HBM).
         Returns disp16 int16 [h][w] (-16 invalid), or dict(disp16, rect, S) when want_rect / want_sum."""
@@ -2847,6 +3023,9 @@ class Context:
 
     def consist(self) -> "Consist":
         return Consist(self)
+
+    def carve(self) -> "Carve":
+        return Carve(self)
 
     def clean(self) -> "Clean":
         return Clean(self)

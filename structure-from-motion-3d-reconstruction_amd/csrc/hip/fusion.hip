@@ -590,3 +590,16 @@ int sfmx_fusion_device_volume(const sfmx_fusion* fu, const double** sum, const i
   *p = fu->p;
   return fu->n;
 }
+
+int sfmx_fusion_mutable_volume(sfmx_ctx* ctx, sfmx_fusion* fu, double** sum, int32_t** count, sfmx_fusion_params* p) {
+  SFMX_REQUIRE(ctx, ctx && fu && p);
+  *p = fu->p;
+  if (!sum || !count) return SFMX_OK;  // the parameters alone: the object is not touched
+  const int rc = sfmx_fusion_integrate(ctx, fu);
+  if (rc != SFMX_OK) return rc;
+  fu->resident = -1;  // the caller changes the volume: the surface kept on the device is no longer its surface
+  fu->cur_v = fu->cur_f = -1;
+  *sum = fu->sum;
+  *count = fu->cnt;
+  return SFMX_OK;
+}

@@ -152,6 +152,13 @@ int sfmx_fusion_device_mesh(const sfmx_fusion* fu, const double** verts, const d
 // fusion.hip: the integrated volume on the device (sum double / count int32 [nz][ny][nx]) and the parameters it was created
 // with; returns the number of grid points, or -1 while views are pending (integrate first)
 int sfmx_fusion_device_volume(const sfmx_fusion* fu, const double** sum, const int32_t** count, sfmx_fusion_params* p);
+// fusion.hip: integrates the pending views, then hands out the volume for writing (sum double / count int32 [nz][ny][nx]) with
+// the parameters it was created with; the surface cached on the device is dropped, as sfmx_fusion_reset drops it.  With sum or
+// count NULL only *p is filled and the object is not touched (a caller checks the grid before it takes the arrays).
+int sfmx_fusion_mutable_volume(sfmx_ctx* ctx, sfmx_fusion* fu, double** sum, int32_t** count, sfmx_fusion_params* p);
+// carve.hip: the hull of the last successful run on the device (hull double / views int32 [nz][ny][nx]), its grid and the
+// min_views that defines a point; returns the number of grid points, or -1 before a successful run
+int sfmx_carve_device_volume(const sfmx_carve* cv, const double** hull, const int32_t** views, sfmx_carve_volume* vol, int* min_views);
 // clean.hip: the cleaned mesh of the last successful run on the device (verts double [n'][3], faces int32 [*n_faces][3]);
 // returns n', or -1 before a successful run
 int sfmx_clean_device_mesh(const sfmx_clean* cl, const double** verts, const int32_t** faces, int* n_faces);

@@ -291,13 +291,16 @@ struct sfmx_stereo {
   uint16_t* S = nullptr;
   int16_t* d16 = nullptr;
   int *lab = nullptr, *size = nullptr;
+  bool d16_current = true;  // false after sfmx_stereo_rectify: the map no longer belongs to the rectified images
   StageTimer t;
 };
 
+// after a rectification alone there is no map: NULL and a size of 0 x 0, which every _add_stereo_view entry that takes the map
+// refuses as a view of another size
 const int16_t* sfmx_stereo_device_disp16(const sfmx_stereo* st, int* w, int* h) {
-  *w = st->w;
-  *h = st->h;
-  return st->d16;
+  *w = st->d16_current ? st->w : 0;
+  *h = st->d16_current ? st->h : 0;
+  return st->d16_current ? st->d16 : nullptr;
 }
 
 const uint8_t* sfmx_stereo_device_rect_left(const sfmx_stereo* st, int* w, int* h) {
@@ -373,6 +376,7 @@ int sfmx_stereo_disparity(sfmx_ctx* ctx, sfmx_stereo* st, const uint8_t* img_l, 
                           const double* H_r, int16_t* disp16_out, uint8_t* rect_out, uint16_t* sum_out) {
   SFMX_REQUIRE(ctx, ctx && st && img_l && img_r && H_l && H_r && disp16_out);
   SFMX_HIP(ctx, hipSetDevice(ctx->device));
+  st->d16_current = true;
   const int w = st->w, h = st->h, D = st->p.num_disparities;
   const size_t n = (size_t)w * h;
   hipStream_t s = ctx->stream;
@@ -420,6 +424,34 @@ int sfmx_stereo_disparity(sfmx_ctx* ctx, sfmx_stereo* st, const uint8_t* img_l, 
   SFMX_HIP(ctx, hipMemcpyAsync(disp16_out, st->d16, n * 2, hipMemcpyDeviceToHost, s));
   if (rect_out) SFMX_HIP(ctx, hipMemcpyAsync(rect_out, st->rect, 2 * n, hipMemcpyDeviceToHost, s));
   if (sum_out) SFMX_HIP(ctx, hipMemcpyAsync(sum_out, st->S, n * (size_t)D * 2, hipMemcpyDeviceToHost, s));
+  SFMX_HIP(ctx, hipStreamSynchronize(s));
+  st->t.us = 0.0;
+  st->t.collect(ctx);
+  return SFMX_OK;
+}
+
+int sfmx_stereo_rectify(sfmx_ctx* ctx, sfmx_stereo* st, const uint8_t* img_l, const uint8_t* img_r, int on_device, const double* H_l,
+                        const double* H_r) {
+  SFMX_REQUIRE(ctx, ctx && st && img_l && img_r && H_l && H_r);
+  SFMX_HIP(ctx, hipSetDevice(ctx->device));
+  st->d16_current = false;
+  const int w = st->w, h = st->h;
+  const size_t n = (size_t)w * h;
+  hipStream_t s = ctx->stream;
+  const uint8_t *il = img_l, *ir = img_r;
+  if (!on_device) {
+    SFMX_HIP(ctx, hipMemcpyAsync(st->img, img_l, n, hipMemcpyHostToDevice, s));
+    SFMX_HIP(ctx, hipMemcpyAsync(st->img + n, img_r, n, hipMemcpyHostToDevice, s));
+    il = st->img;
+    ir = st->img + n;
+  }
+  H9 hl, hr;
+  std::memcpy(hl.a, H_l, sizeof hl.a);
+  std::memcpy(hr.a, H_r, sizeof hr.a);
+  SFMX_HIP(ctx, st->t.begin(ctx));
+  k_st_rectify<<<dim3((unsigned)((w + 255) / 256), (unsigned)h, 2u), 256, 0, s>>>(il, ir, hl, hr, w, h, st->rect, st->valid);
+  SFMX_HIP(ctx, hipGetLastError());
+  SFMX_HIP(ctx, st->t.end(ctx));
   SFMX_HIP(ctx, hipStreamSynchronize(s));
   st->t.us = 0.0;
   st->t.collect(ctx);

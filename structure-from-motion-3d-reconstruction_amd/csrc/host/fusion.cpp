@@ -134,6 +134,17 @@
 #pragma weak sfmx_photo_run
 #pragma weak sfmx_photo_read
 #pragma weak sfmx_photo_sizes
+#pragma weak sfmx_stereo_rectify
+#pragma weak sfmx_carve_check_params
+#pragma weak sfmx_carve_create
+#pragma weak sfmx_carve_destroy
+#pragma weak sfmx_carve_add_stereo_view
+#pragma weak sfmx_carve_view_count
+#pragma weak sfmx_carve_inside_pixels
+#pragma weak sfmx_carve_run
+#pragma weak sfmx_carve_apply
+#pragma weak sfmx_carve_store
+#pragma weak sfmx_carve_count
 
 namespace {
 
@@ -155,7 +166,9 @@ struct Guard {
   sfmx_texture* tx = nullptr;
   sfmx_level* lv = nullptr;
   sfmx_photo* ph = nullptr;
+  sfmx_carve* cv = nullptr;
   ~Guard() {
+    if (cv) sfmx_carve_destroy(ctx, cv);
     if (ph) sfmx_photo_destroy(ctx, ph);
     if (lv) sfmx_level_destroy(ctx, lv);
     if (tx) sfmx_texture_destroy(ctx, tx);
@@ -529,6 +542,26 @@ int sfmx_host_fusion_mesh_ph(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
                              sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_level_request* level, sfmx_photo_request* photo,
                              sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
+  return sfmx_host_fusion_mesh_cv(ctx, images, on_device, n, w, h, K9, poses12, pairs, m, sp, fp, app, cs, pair_counts, clean, clean_counts, gt,
+                                  ev, render, align, simplify, simplify_counts, smooth, smooth_counts, fill, fill_counts, raster, visib, texture,
+                                  level, photo, nullptr, res, ply_path, warn, warn_cap);
+}
+
+void sfmx_host_carve_free(sfmx_carve_request* carve) {
+  if (!carve) return;
+  std::free(carve->inside_pixels);
+  carve->inside_pixels = nullptr;
+}
+
+int sfmx_host_fusion_mesh_cv(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_level_request* level, sfmx_photo_request* photo,
+                             sfmx_carve_request* carve, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap) {
   if (!ctx || (n > 0 && (!images || !poses12)) || n < 0 || m < 0 || (m > 0 && !pairs) || !K9 || !sp || !fp || !res)
     return SFMX_ERR_INVALID;
   *res = sfmx_fusion_result_ex{};
@@ -583,6 +616,22 @@ int sfmx_host_fusion_mesh_ph(sfmx_ctx* ctx, const uint8_t* const* images, int on
     pp.z_min = xp.z_min;
     if (sfmx_photo_check_params(&pp) != SFMX_OK) return SFMX_ERR_INVALID;
   }
+  sfmx_carve_params kp{};
+  if (carve) {
+    for (int32_t& c : carve->counts) c = 0;
+    carve->n_views = 0;
+    carve->inside_pixels = nullptr;
+    if (!&sfmx_carve_check_params || !&sfmx_carve_create || !&sfmx_carve_destroy || !&sfmx_carve_add_stereo_view || !&sfmx_carve_view_count ||
+        !&sfmx_carve_inside_pixels || !&sfmx_carve_run || !&sfmx_carve_apply || !&sfmx_carve_store || !&sfmx_carve_count || !&sfmx_stereo_rectify)
+      return SFMX_ERR_UNSUPPORTED;
+    kp = carve->params;
+    if (kp.trunc == 0.0) kp.trunc = fp->trunc == 0.0 ? 4.0 * fp->voxel : fp->trunc;  // the volume's resolved trunc
+    if (sfmx_carve_check_params(&kp) != SFMX_OK || carve->threshold < 1 || carve->threshold > 255 ||
+        (carve->hull_only != 0 && carve->hull_only != 1))
+      return SFMX_ERR_INVALID;
+    if (carve->hull_only && (cs || align || app)) return SFMX_ERR_INVALID;  // they need the disparity maps
+  }
+  const bool hull_only = carve && carve->hull_only;
   if (!&sfmx_fusion_create || !&sfmx_stereo_disparity) return SFMX_ERR_UNSUPPORTED;
   if (app && (!&sfmx_shade_create || !&sfmx_fusion_extract_normals)) return SFMX_ERR_UNSUPPORTED;
   if (cs && (!&sfmx_consist_create || !&sfmx_fusion_add_consist_view)) return SFMX_ERR_UNSUPPORTED;
@@ -715,6 +764,10 @@ int sfmx_host_fusion_mesh_ph(sfmx_ctx* ctx, const uint8_t* const* images, int on
     rc = sfmx_photo_create(ctx, &g.ph);
     if (rc != SFMX_OK) return rc;
   }
+  if (carve) {
+    rc = sfmx_carve_create(ctx, &g.cv);
+    if (rc != SFMX_OK) return rc;
+  }
   std::vector<int16_t> d16((size_t)w * h);  // sfmx_stereo_disparity always returns the map to the host
   for (int q = 0; q < m; q++) {
     const int a = pairs[2 * q], b = pairs[2 * q + 1];
@@ -739,7 +792,8 @@ int sfmx_host_fusion_mesh_ph(sfmx_ctx* ctx, const uint8_t* const* images, int on
     }
     const uint8_t* il = r.swapped ? images[b] : images[a];
     const uint8_t* ir = r.swapped ? images[a] : images[b];
-    rc = sfmx_stereo_disparity(ctx, g.st, il, ir, on_device, r.H_l, r.H_r, d16.data(), nullptr, nullptr);
+    rc = hull_only ? sfmx_stereo_rectify(ctx, g.st, il, ir, on_device, r.H_l, r.H_r)
+                   : sfmx_stereo_disparity(ctx, g.st, il, ir, on_device, r.H_l, r.H_r, d16.data(), nullptr, nullptr);
     if (rc != SFMX_OK) return rc;
     sfmx_fusion_view v{};
     std::memcpy(v.R_rw, r.R_rw, sizeof v.R_rw);
@@ -762,8 +816,12 @@ int sfmx_host_fusion_mesh_ph(sfmx_ctx* ctx, const uint8_t* const* images, int on
         v = ar.view;
     }
     // with cs the view waits in the consist object: its filtered map is queued after the loop
-    rc = cs ? sfmx_consist_add_stereo_view(ctx, g.cs, &v, g.st) : sfmx_fusion_add_stereo_view(ctx, g.fu, &v, g.st);
+    rc = hull_only ? SFMX_OK : cs ? sfmx_consist_add_stereo_view(ctx, g.cs, &v, g.st) : sfmx_fusion_add_stereo_view(ctx, g.fu, &v, g.st);
     if (rc != SFMX_OK) return rc;
+    if (carve) {  // the silhouette of the view as it entered the volume
+      rc = sfmx_carve_add_stereo_view(ctx, g.cv, &v, g.st, carve->threshold, kp.cap);
+      if (rc != SFMX_OK) return rc;
+    }
     if (cs) listed.push_back(q);
     if (app) {
       rc = sfmx_shade_add_stereo_view(ctx, g.sh, &v, g.st);
@@ -777,7 +835,7 @@ int sfmx_host_fusion_mesh_ph(sfmx_ctx* ctx, const uint8_t* const* images, int on
       rc = sfmx_texture_add_stereo_view(ctx, g.tx, &v, g.st);
       if (rc != SFMX_OK) return rc;
     }
-    res->n_views++;
+    if (!hull_only) res->n_views++;  // pairs integrated: none with hull_only (carve->n_views counts its silhouettes)
   }
   if (cs) {
     rc = sfmx_consist_filter(ctx, g.cs, cs);
@@ -799,6 +857,19 @@ int sfmx_host_fusion_mesh_ph(sfmx_ctx* ctx, const uint8_t* const* images, int on
   }
   rc = sfmx_fusion_integrate(ctx, g.fu);
   if (rc != SFMX_OK) return rc;
+  if (carve && sfmx_carve_view_count(g.cv) > 0) {
+    const sfmx_carve_volume vol{{fp->origin[0], fp->origin[1], fp->origin[2]}, fp->voxel, fp->nx, fp->ny, fp->nz};
+    rc = sfmx_carve_run(ctx, g.cv, &vol, &kp);
+    // hull_only: the counters come from the hull alone (changed stays 0: there was no volume to change), then the hull is stored
+    if (rc == SFMX_OK) rc = hull_only ? sfmx_carve_count(ctx, g.cv, &kp, carve->counts) : sfmx_carve_apply(ctx, g.cv, g.fu, &kp, carve->counts);
+    if (rc == SFMX_OK && hull_only) rc = sfmx_carve_store(ctx, g.cv, g.fu);
+    if (rc != SFMX_OK) return rc;
+    carve->n_views = sfmx_carve_view_count(g.cv);
+    carve->inside_pixels = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (size_t)carve->n_views));
+    if (!carve->inside_pixels) return SFMX_ERR_INVALID;
+    rc = sfmx_carve_inside_pixels(g.cv, carve->inside_pixels);
+    if (rc != SFMX_OK) return rc;
+  }
   int nv = 0, nf = 0;
   rc = sfmx_fusion_extract(ctx, g.fu, nullptr, 0, nullptr, 0, &nv, &nf);
   if (rc != SFMX_OK) return rc;

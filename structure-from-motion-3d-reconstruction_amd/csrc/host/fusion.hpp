@@ -338,4 +338,35 @@ int sfmx_host_fusion_mesh_ph(sfmx_ctx* ctx, const uint8_t* const* images, int on
                              int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
                              sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_level_request* level, sfmx_photo_request* photo,
                              sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
+
+// sfmx_host_fusion_mesh_ph with the volume carved by the pairs' silhouettes.  carve = NULL: exactly
+// sfmx_host_fusion_mesh_ph.  Otherwise the silhouette of every integrated pair is its left rectified picture at `threshold` under
+// the pair's left rectified camera (the refined one with align), kept as a signed squared distance map at params.cap; after the
+// last integration and before the extraction the hull of all of them is computed on the volume's grid (params.trunc == 0 stands
+// for the volume's resolved trunc) and the volume is carved with it (sfmx_carve_apply: params.margin, params.mode), so that the
+// surface, the normals, the ray-cast renders and every later stage see the carved volume.  hull_only = 1 skips the disparities
+// and the integration: each pair is only rectified, the hull is stored into the empty volume (sfmx_carve_store) and the rest of
+// the chain runs on it; it is refused (SFMX_ERR_INVALID) together with cs, align and app, which need the disparity maps.  The
+// request's outputs are filled: counts (defined, outside, changed; with hull_only the mode is not used, changed is 0 and the result's n_views, the pairs
+// integrated, is 0), n_views and inside_pixels
+// [n_views], the inside pixels of each view (malloc'ed here, NULL without a view; release it with sfmx_host_carve_free).
+// Without an integrated pair nothing is carved.
+struct sfmx_carve_request {
+  sfmx_carve_params params;
+  int threshold;  // 1 .. 255
+  int hull_only;  // 0 or 1
+  int32_t counts[3];
+  int32_t n_views;
+  int32_t* inside_pixels;
+};
+void sfmx_host_carve_free(sfmx_carve_request* carve);
+int sfmx_host_fusion_mesh_cv(sfmx_ctx* ctx, const uint8_t* const* images, int on_device, int n, int w, int h, const double* K9,
+                             const double* poses12, const int32_t* pairs, int m, const sfmx_stereo_params* sp,
+                             const sfmx_fusion_params* fp, const sfmx_shade_params* app, const sfmx_consist_params* cs,
+                             int32_t* pair_counts, const sfmx_clean_params* clean, int32_t* clean_counts, const sfmx_surface_gt* gt,
+                             sfmx_surface_eval_result* ev, const sfmx_render_request* render, const sfmx_align_request* align,
+                             const sfmx_simplify_params* simplify, int32_t* simplify_counts, const sfmx_smooth_params* smooth,
+                             int32_t* smooth_counts, const sfmx_fill_params* fill, int32_t* fill_counts, const sfmx_raster_request* raster,
+                             sfmx_visib_request* visib, sfmx_texture_request* texture, sfmx_level_request* level, sfmx_photo_request* photo,
+                             sfmx_carve_request* carve, sfmx_fusion_result_ex* res, const char* ply_path, char* warn, int warn_cap);
 }

@@ -269,6 +269,14 @@ class PhotoRequest(ctypes.Structure):
                 ("hist", POINTER(ctypes.c_int64))]
 
 
+CARVE_KEYS = ("threshold", "cap", "margin", "mode", "min_views", "hull_only")
+
+
+class CarveRequest(ctypes.Structure):
+    _fields_ = [("params", capi.CarveParams), ("threshold", c_int), ("hull_only", c_int), ("counts", c_int * 3), ("n_views", c_int),
+                ("inside_pixels", POINTER(c_int))]
+
+
 def write_pgm(path: str, image) -> None:
     """a u8 [h][w] image as a binary PGM (P5)"""
     image = np.ascontiguousarray(image, np.uint8)
@@ -496,7 +504,7 @@ def _split_fusion_params(params: dict):
 
 def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=None, ply_path: str | None = None, appearance=False,
          consistency=False, clean=False, evaluate=None, render=None, align=False, simplify=False, smooth=False, fill=False, raster=None,
-         visibility=False, texture=False, level=False, photo=False, palign=False, **params) -> dict:
+         visibility=False, texture=False, level=False, photo=False, palign=False, carve=False, **params) -> dict:
     """Multi-pair depth fusion: per pair rectify (host) -> disparity (device) -> one TSDF view; then integrate and extract
     the surface (device).  images: u8 [n][h][w] host array, or a list of device pointers (ints) with shape=(h, w).
     poses: [n] camera->world poses (12 doubles or (R, c)); pairs: [(a, b), ...] indices into images.  The volume is
@@ -576,7 +584,32 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
     capi.PALIGN_DEFAULTS keys) (needs texture) -- after the chain has returned, each listed camera is registered to the final
     textured mesh by direct photometric alignment on the device (view_register, on the levelled atlas with level).
     The dict gains palign = [view_register's dict per camera] ([] for a mesh without faces).  Everything else is what it is
-    without palign."""
+    without palign.
+    carve: True, or dict(threshold=1, cap=16, margin=0.5, mode="intersect" | "clear", min_views=1, hull_only=False) -- shape from
+    silhouette: the silhouette of each integrated pair is its left rectified picture at `threshold` (1 .. 255) under
+    the pair's left rectified camera (the refined one with align); after the last integration and before the extraction, the normals
+    and render, every grid point that some camera sees more than `margin` (in units of the volume's trunc) outside its silhouette
+    is made undefined (clear) or given the hull's value where the volume holds none or a smaller one (intersect).  The dict gains
+    carve = dict(defined, outside, changed, inside_pixels=[per view]).  A trunc given to the fusion is the hull's too.
+    hull_only=True skips the disparities and the integration,
+    stores the hull itself in the volume and lets the rest of the chain run on it (views, the pairs integrated, is then 0, mode is
+    not used and changed is 0); it raises ValueError together with consistency,
+    align and appearance.  The object must lie inside every picture (a rectified picture is 0 where its source has no pixel)."""
+    kq = None
+    if carve is not False and carve is not None:  # carve={} is the defaults
+        kkw = {} if carve is True else dict(carve)
+        unknown = set(kkw) - set(CARVE_KEYS)
+        if unknown:
+            raise TypeError(f"unknown carve parameters {sorted(unknown)}")
+        k_thr, k_hull = kkw.pop("threshold", 1), kkw.pop("hull_only", False)
+        if isinstance(k_thr, bool) or not isinstance(k_thr, (int, np.integer)) or not isinstance(k_hull, (bool, np.bool_)):
+            raise TypeError("carve: threshold is an int, hull_only a bool")
+        kp = capi.carve_params(**kkw)
+        if not 1 <= int(k_thr) <= 255 or not capi.carve_check_params(**kkw):
+            raise ValueError("carve parameters outside their range")
+        if k_hull and (consistency or align or appearance):
+            raise ValueError("carve hull_only has no disparity maps: not together with consistency, align or appearance")
+        kq = CarveRequest(kp, int(k_thr), int(bool(k_hull)))
     lib = load_host_library()
     if isinstance(images, (list, tuple)) and images and isinstance(images[0], int):
         h, w = shape
@@ -776,12 +809,28 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         seed = int(gkw.pop("seed", 1))
         aouts = (capi.AlignResult * max(len(pr), 1))()
         aq = AlignRequest(seed, capi.align_params(disp_min=fp.disp_min, **gkw), aouts)
-    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None or hp is not None or zq is not None or vq is not None or xq is not None:
+    if ap is not None or cp is not None or lp is not None or gt is not None or rq is not None or aq is not None or mp is not None or tp is not None or hp is not None or zq is not None or vq is not None or xq is not None or kq is not None:
         rex = FusionResultEx()
         head = (ctx.h_, ptrs, c_int(on_dev), c_int(n), c_int(w), c_int(h), K.ctypes.data_as(dp), poses12.ctypes.data_as(dp),
                 pr.ctypes.data_as(POINTER(c_int)), c_int(len(pr)), byref(sp), byref(fp), byref(ap) if ap is not None else None)
         tail = (byref(rex), ply_path.encode() if ply_path else None, warn, c_int(len(warn)))
-        if pq is not None:
+        if kq is not None:
+            rc = lib.sfmx_host_fusion_mesh_cv(*head, byref(cp) if cp is not None else None,
+                                              counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
+                                              byref(lp) if lp is not None else None,
+                                              lcounts.ctypes.data_as(POINTER(c_int)) if lp is not None else None,
+                                              byref(gt) if gt is not None else None, byref(ev) if gt is not None else None,
+                                              byref(rq) if rq is not None else None, byref(aq) if aq is not None else None,
+                                              byref(mp) if mp is not None else None,
+                                              mcounts.ctypes.data_as(POINTER(c_int)) if mp is not None else None,
+                                              byref(tp) if tp is not None else None,
+                                              tcounts.ctypes.data_as(POINTER(c_int)) if tp is not None else None,
+                                              byref(hp) if hp is not None else None,
+                                              hcounts.ctypes.data_as(POINTER(c_int)) if hp is not None else None,
+                                              byref(zq) if zq is not None else None, byref(vq) if vq is not None else None,
+                                              byref(xq) if xq is not None else None, byref(lq) if lq is not None else None,
+                                              byref(pq) if pq is not None else None, byref(kq), *tail)
+        elif pq is not None:
             rc = lib.sfmx_host_fusion_mesh_ph(*head, byref(cp) if cp is not None else None,
                                               counts.ctypes.data_as(POINTER(c_int)) if cp is not None else None,
                                               byref(lp) if lp is not None else None,
@@ -908,8 +957,14 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
         else:
             rc = lib.sfmx_host_fusion_mesh_ex(*head, *tail)
         if rc != capi.SFMX_OK:
+            if kq is not None:
+                lib.sfmx_host_carve_free(byref(kq))
             raise capi.SfmxError(rc, (ctx.lib.sfmx_last_error(ctx.h_) or b"").decode() or "fuse")
         try:
+            if kq is not None:
+                kn = int(kq.n_views)
+                car = dict(zip(capi.CARVE_COUNTS, (int(c) for c in kq.counts)),
+                           inside_pixels=[int(kq.inside_pixels[i]) for i in range(kn)] if kn else [])
             if vq is not None:
                 vn, vm = int(vq.n_in), int(vq.m_in)
                 vis = dict(face_views=np.ctypeslib.as_array(vq.face_views, (vm,)).astype(np.int32) if vm else np.zeros(0, np.int32),
@@ -954,6 +1009,8 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                 out["vertex_views"] = np.ctypeslib.as_array(rex.views, (nv,)).astype(np.int32) if nf else np.zeros(0, np.int32)
         finally:
             lib.sfmx_host_fusion_free_ex(byref(rex))
+            if kq is not None:
+                lib.sfmx_host_carve_free(byref(kq))
             if vq is not None:
                 lib.sfmx_host_visib_free(byref(vq))
             if xq is not None:
@@ -962,6 +1019,8 @@ def fuse(ctx: capi.Context, images, K, poses, pairs, origin, voxel, dims, shape=
                 lib.sfmx_host_level_free(byref(lq))
             if pq is not None:
                 lib.sfmx_host_photo_free(byref(pq))
+        if kq is not None:
+            out["carve"] = car
         if pq is not None:
             out["photo"] = pho
             if photo_prefix:
@@ -1075,7 +1134,7 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
     pair's view to the volume before it enters it; 'simplify' (True or a dict, as fuse) simplifies the final surface by exact vertex
     clustering; 'smooth' (True or a dict, as fuse) smooths it with the exact Taubin filter first; 'fill' (True or a dict, as fuse) fills its small
     holes before that; 'raster' (a dict, as fuse) renders the final mesh from further cameras; 'visibility' (a dict, as fuse) first removes
-    the faces no pair's camera sees from the front; 'texture' (a dict, as fuse) bakes a texture atlas for the final mesh; 'level' (True or a dict, as fuse, with texture) levels its seams; 'photo' (True or a dict, as fuse, with texture) renders the textured mesh back into the texture's views and measures the photometric error; 'palign' (a dict, as fuse, with texture) registers further cameras to the textured mesh.  The run itself, its log and every other output are unchanged.
+    the faces no pair's camera sees from the front; 'texture' (a dict, as fuse) bakes a texture atlas for the final mesh; 'level' (True or a dict, as fuse, with texture) levels its seams; 'photo' (True or a dict, as fuse, with texture) renders the textured mesh back into the texture's views and measures the photometric error; 'palign' (a dict, as fuse, with texture) registers further cameras to the textured mesh; 'carve' (True or a dict, as fuse) carves the volume with the pairs' silhouettes, or with hull_only builds the surface from them alone.  The run itself, its log and every other output are unchanged.
     comms (optional): (ba, ransac) capi.Comm objects -- every rank runs the same sequence, BA points and RANSAC hypotheses
     are sharded over the ranks: `ba` carries the S | b all-reduce of lane B, `ransac` the winner merges the geometry
     thread issues in program order (csrc/host/pipeline.hpp: PipelineConfig)."""
@@ -1151,10 +1210,11 @@ def run(ctx: capi.Context, images: np.ndarray | None, names, K, lat=None, lon=No
         level = fz.pop("level", False)
         photo = fz.pop("photo", False)
         palign = fz.pop("palign", False)
+        carve = fz.pop("carve", False)
         out["fused_mesh"] = fuse(ctx, imgs, K, out["kf_poses"], pairs, origin, voxel, dims, shape=fshape, ply_path=ply,
                                  appearance=appearance, consistency=consistency, clean=clean, evaluate=evaluate, render=render, align=align,
                                  simplify=simplify, smooth=smooth, fill=fill, raster=raster, visibility=visibility, texture=texture,
-                                 level=level, photo=photo, palign=palign, **fz)
+                                 level=level, photo=photo, palign=palign, carve=carve, **fz)
     return out
 
 
